@@ -12,7 +12,16 @@ group per round) and a 9:1 ReadIndex:write mix batched into one ReadIndex
 ctx per group per round, one LocalTick per round.  Multi-GPU: groups are
 sharded over ranks (weak scaling, no data-path collective).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
+                       [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K rounds and prints the result
+line.  --full adds the secondary measurements after the timed region (KV
+occupancy, wire encode / ingest, host-staged and step-worker rounds, the
+CPU oracle's baseline, C4 across the ranks of a multi-GPU run).
+--dump-outputs writes a seeded sample of what the last timed round left
+for its callers (dump_outputs); the inputs are seeded, so two builds can be
+compared array for array.
 """
 import argparse
 import json
@@ -31,6 +40,7 @@ READS_PER_CTX = 9      # C3: 9 ReadIndex reads per write, one ctx per round
 # 512 slots (tests/test_gpu_fullsize.py pins the timed rounds at this fill)
 C3_KV_FILL = 1536
 KEY_SPACE = 256        # K = 256 keys per group
+MAX_BATCHES = 128      # staged input batches resident at once (--steps)
 
 
 def alg_bytes_per_group_round(R=3, k=1, P=16, reads=True, spread=False):
@@ -81,6 +91,19 @@ def parse():
                          "WORLD_SIZE")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the secondary "
+                         "measurements that are on by default under this "
+                         "option: the KV occupancy sample, the wire encode "
+                         "and ingest, host-staged and step-worker rounds, "
+                         "the CPU baseline and (N > 1) C4 across the ranks; "
+                         "without it a run times its steps and prints the "
+                         "line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed "
+                         "round left for its callers as DIR/<name>.npy "
+                         "(dump_outputs: a fixed, seeded sample of the "
+                         "groups)")
     ap.add_argument("--workload", default="c3",
                     choices=["c2", "c3", "c4", "c5"],
                     help="c3: groups sharded over GPUs, replicas "
@@ -157,10 +180,13 @@ def parse():
                          "rehearse the multi-rank control flow with several "
                          "ranks on one GPU")
     ap.add_argument("--no-wire", action="store_true",
-                    help="skip the off-GPU wire encode measurement (C3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: skip the off-GPU wire encode measurement "
+                         "(C3)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU oracle's timed sample")
     ap.add_argument("--no-ingest", action="store_true",
-                    help="skip the receiving-side wire ingest measurement")
+                    help="--full: skip the receiving-side wire ingest "
+                         "measurement")
     ap.add_argument("--exchange", default="counted",
                     choices=["fixed", "counted"],
                     help="c4 plane exchange: sized by an all_gather of "
@@ -186,7 +212,8 @@ def parse():
     ap.add_argument("--host-staged", type=int, default=-1,
                     help="after the timed region, also time rounds whose "
                          "proposals come from host memory through "
-                         "drb_stage_proposals (default: on for c2/c3, N=1)")
+                         "drb_stage_proposals (default: on under --full for "
+                         "c2/c3, N=1)")
     ap.add_argument("--rounds-per-call", type=int, default=-1,
                     help="timed rounds per drb_step_rounds call (a chunk of "
                          "every group: plain rounds from one C call); -1: 16 "
@@ -200,7 +227,7 @@ def parse():
                     help="with --gpus N > 1 and a co-resident workload, also "
                          "time C4 across the ranks through the C ABI's RCCL "
                          "exchange (drb_exchange_rccl*; gloo: a rehearsal "
-                         "through host memory); default on")
+                         "through host memory); default: on under --full")
     ap.add_argument("--c4-groups", type=int, default=1 << 20,
                     help="groups of that C4 run (in total)")
     ap.add_argument("--c4-timeout", type=int, default=240,
@@ -210,7 +237,8 @@ def parse():
                          "worker rounds: host-staged proposals, the round, "
                          "and its ReadyToReads, read results and applied "
                          "entries back in pinned host memory "
-                         "(drb_worker_export; default: on for c3, N=1)")
+                         "(drb_worker_export; default: on under --full for "
+                         "c3, N=1)")
     return ap.parse_args()
 
 
@@ -331,7 +359,7 @@ def run_c4_local(args):
     N, G, k = args.local_ranks, args.groups, args.k
     R = args.replicas or 5
     lanes = (G + N - 1) // N
-    NP = max(8, args.steps)
+    NP = min(max(8, args.steps), MAX_BATCHES)
     seed = ddist.BASE_SEED
     torch.cuda.set_device(0)
     engs = [Engine(num_groups=lanes, num_replicas=R, window=32, cmd_cap=32,
@@ -355,7 +383,7 @@ def run_c4_local(args):
         for e in engs:
             e.gen_kv_proposals(0, k, KEY_SPACE, 4, seed, WARM + i)
         rnd(i, 0, True)
-    for b in range(args.steps):
+    for b in range(min(NP, args.steps)):
         for e in engs:
             e.gen_kv_proposals(b, k, KEY_SPACE, 4, seed, TIMED + b)
     for e in engs:
@@ -367,13 +395,16 @@ def run_c4_local(args):
     te = max(1, args.tick_every or 1)
     t0 = time.perf_counter()
     for i in range(K):
-        rnd(i, i, i % te == 0)
+        rnd(i, i % NP, i % te == 0)
     for e in engs:
         e.sync()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     outs = [e.read_counters(reset=True) for e in engs]
     xb = [e.exchange_bytes(reset=True) for e in engs]
+    if args.dump_outputs:
+        for r, (e, o) in enumerate(zip(engs, outs)):
+            dump_outputs(args.dump_outputs, e, o, K, False, "_rank%d" % r)
     committed = sum(o.committed_entries for o in outs)
     fb = sum(o.fallbacks + o.errors for o in outs)
     alg = alg_bytes_per_group_round(R, k, 16, False, True) * G
@@ -439,7 +470,7 @@ def run_c4_cross(args, world, rank, local, gloo):
     from dragonboat_amd.engine import Engine
     G, R, k = args.c4_groups, 5, 1
     lanes = (G + world - 1) // world
-    NP = max(8, args.steps)
+    NP = min(max(8, args.steps), MAX_BATCHES)
     seed = ddist.BASE_SEED
     red = "cpu" if gloo else "cuda"
     dev = torch.device("cuda", local)
@@ -498,7 +529,7 @@ def run_c4_cross(args, world, rank, local, gloo):
                 xchg(mode)
             r0 += args.warmup
             K = args.steps
-            for b in range(K):
+            for b in range(min(NP, K)):
                 eng.gen_kv_proposals(b, k, KEY_SPACE, 4, seed, TIMED + r0 + b)
             eng.sync()
             eng.read_counters(reset=True)
@@ -508,7 +539,7 @@ def run_c4_cross(args, world, rank, local, gloo):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for i in range(K):
-                eng.step_async(tick=True, prop_slot=i)
+                eng.step_async(tick=True, prop_slot=i % NP)
                 xchg(mode)
             eng.sync()
             torch.cuda.synchronize()
@@ -535,6 +566,96 @@ def run_c4_cross(args, world, rank, local, gloo):
         if comm is not None:
             comm.close()
         eng.close()
+
+
+DUMP_RUNS, DUMP_RUN = 64, 64  # --dump-outputs: 64 runs of 64 groups
+# the drb_replica_state fields a round's inputs decide; the tick and quiesce
+# clocks and the timeout draws are left out, they follow the LocalTick
+# cadence, which a run derives from the wall clock (--tick-ms)
+DUMP_REPLICA = ["shard_id", "replica_id", "term", "vote", "leader_id",
+                "applied", "committed", "processed", "last_index",
+                "marker_index", "applied_to_index", "applied_to_term",
+                "applied_index", "sm_index", "sm_term", "kv_count", "role",
+                "flags", "fallback_reason"]
+DUMP_COUNTERS = ["committed_entries", "applied_entries", "ready_to_reads",
+                 "dropped_read_indexes", "fallbacks", "errors",
+                 "reads_served", "reads_deferred", "saved_entries",
+                 "saved_bytes", "dropped_proposals"]
+
+
+def dump_outputs(path, eng, out, steps, reads, suffix=""):
+    """--dump-outputs: what the last timed round left for its callers, as
+    float64 arrays path/<name><suffix>.npy (every value is below 2^53, so
+    exact; a 64-bit word is stored as its low and high 32 bits):
+      counters      DUMP_COUNTERS of the timed rounds (drb_read_counters)
+                    and the number of timed rounds
+      replicas      DUMP_REPLICA of every replica of the sampled groups
+                    (drb_export_replicas), then the match and next of its
+                    first R remotes
+      applied       group, slot, index, key lo, key hi, client lo, client
+                    hi, series_id, value, ignored of the entries the last
+                    round applied (drb_apply_results, every slot)
+      ready         group, index, ctx_low lo, ctx_low hi, ctx_high of slot
+                    0's ReadyToReads of the last round
+      read_results  group, index, read, key lo, key hi, found, vlen, value
+                    of the reads slot 0 served in the last round
+                    (drb_export_read_results; with read results on)
+      kv            group, slot, key lo, key hi, value of the first group
+                    of each run, sorted by key (drb_kv_export)
+    The sample is fixed: DUMP_RUNS runs of DUMP_RUN consecutive groups at
+    seeded offsets (every group of an engine with fewer)."""
+    import numpy as np
+    G, R = eng.G, eng.R
+    if G <= DUMP_RUNS * DUMP_RUN:
+        runs = [(0, G)]
+    else:
+        rng = np.random.RandomState(0x5EED)
+        first = np.unique(rng.randint(0, G // DUMP_RUN, DUMP_RUNS))
+        runs = [(int(f) * DUMP_RUN, DUMP_RUN) for f in first]
+
+    def split(x):
+        x = int(x)
+        return [x & 0xFFFFFFFF, x >> 32]
+
+    rep, app, rdy, rres, kv = [], [], [], [], []
+    for g0, n in runs:
+        for st in eng.export_replicas(g0, n):
+            row = [getattr(st, f) for f in DUMP_REPLICA]
+            for p in range(R):
+                row += [st.remotes[p].match, st.remotes[p].next]
+            rep.append(row)
+        for s in range(R):
+            for (g, idx, key, cid, sid, val, ign) in eng.apply_results(
+                    s, g0, n):
+                app.append([g, s, idx] + split(key) + split(cid) +
+                           [sid, val, ign])
+        for g, lst in sorted(eng.export_ready_batch(0, g0, n).items()):
+            for (idx, lo, hi) in lst:
+                rdy.append([g, idx] + split(lo) + [hi])
+        if reads:
+            for (g, idx, _, j, key, found, vlen, val) in \
+                    eng.export_read_results(0, g0, n):
+                rres.append([g, idx, j] + split(key) + [found, vlen, val])
+        if eng.cfg["kv_val_cap"] <= 4 and not eng.cfg["kv_pool_blocks"]:
+            for s in range(R):
+                for key, val in sorted(eng.kv_export(g0, s).items()):
+                    kv.append([g0, s] + split(int.from_bytes(key, "little")) +
+                              [int.from_bytes(val, "little")])
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, rows, width):
+        a = np.asarray(rows, dtype=np.float64).reshape(-1, width)
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+
+    save("counters", [[getattr(out, f) for f in DUMP_COUNTERS] + [steps]],
+         len(DUMP_COUNTERS) + 1)
+    save("replicas", rep, len(DUMP_REPLICA) + 2 * R)
+    save("applied", app, 10)
+    save("ready", rdy, 5)
+    if reads:
+        save("read_results", rres, 8)
+    if kv:
+        save("kv", kv, 5)
 
 
 def self_launch(args):
@@ -608,8 +729,9 @@ def main():
         args.no_read_index = True  # 16 B writes, k_w = 1
     reads = not args.no_read_index
     # staged input batches: one per timed round, every one with fresh keys,
-    # all resident in HBM before the timed region
-    NP = max(8, args.steps)
+    # all resident in HBM before the timed region (a run of more than
+    # MAX_BATCHES steps goes round them again: a batch is ~100 MB at C3)
+    NP = min(max(8, args.steps), MAX_BATCHES)
     if args.kv_fill < 0:
         args.kv_fill = 0 if (c4 or c5) else C3_KV_FILL
     xch = None
@@ -751,11 +873,11 @@ def main():
         eng.sync()
     args.tick_every = tick_every[0]
     if not c5:  # the timed rounds' inputs, resident before timing starts
-        for b in range(args.steps):
+        for b in range(min(NP, args.steps)):
             stage(b, TIMED_SALT + b)
         eng.sync()
     kv_load = None
-    if not (c4 or c5):
+    if args.full and not (c4 or c5):
         # the KV occupancy the timed rounds run at: distinct keys per
         # replica over a sample of groups (drb_kv_export)
         smp = [g * (G // 64) for g in range(64)]
@@ -812,13 +934,17 @@ def main():
     else:
         for i in range(K):
             ev[i][0].record(stream)
-            step(2 * args.warmup + i, None if c5 else i)
+            step(2 * args.warmup + i, None if c5 else i % NP)
             ev[i][1].record(stream)
     eng.sync()
     torch.cuda.synchronize()
     ddist.barrier()
     t1 = time.perf_counter()
     out = eng.read_counters(reset=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, out, K,
+                     reads and bool(args.read_results),
+                     "_rank%d" % rank if world > 1 else "")
     if phase_dbg:  # cycles per stepped lane of each round phase
         for role, x in eng.debug_phase(reset=True).items():
             print("phase raw %s per round: %s" % (
@@ -901,7 +1027,7 @@ def main():
         chunk_ab["fallbacks"] = out2.fallbacks
         chunk_ab["errors"] = out2.errors
     wire = None
-    if not (c4 or c5 or args.no_wire):
+    if args.full and not (c4 or c5 or args.no_wire):
         # after the timed region: the last round's leader -> follower-slot-1
         # plane as dragonboat's TCP stream (drb_encode_wire), as if every
         # slot-1 replica lived on one remote NodeHost
@@ -1015,7 +1141,8 @@ def main():
     host_staged = None
     step_worker = None
     if args.host_staged < 0:
-        args.host_staged = int(world == 1 and not (c4 or c5) and k == 1 and
+        args.host_staged = int(args.full and world == 1 and
+                               not (c4 or c5) and k == 1 and
                                not args.failover)
     if args.host_staged:
         # the same rounds with this round's proposals staged from host
@@ -1076,7 +1203,8 @@ def main():
                     "layout kernel; the host waits for an upload at the "
                     "next call), timed around the whole loop; not `value`"}
         if args.step_worker < 0:
-            args.step_worker = int(reads and not c2 and args.read_results)
+            args.step_worker = int(args.full and reads and not c2 and
+                                   args.read_results)
         if args.step_worker:
             # engine.processSteps as a whole (engine.go:1304-1364): the
             # entry queue up, the round, and every output a step worker
@@ -1336,11 +1464,11 @@ def main():
                                        "gloo with host staging (one-GPU "
                                        "boxes); this line is its first "
                                        "RCCL run"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # (rank 0 at N = 1 only: the scaling runs keep their ranks' time)
             res["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
     if args.c4_cross < 0:
-        args.c4_cross = int(world > 1 and not c4)
+        args.c4_cross = int(args.full and world > 1 and not c4)
     if args.c4_cross and world > 1:
         # C4 through the C ABI's cross-GPU exchange, after the timed run.
         # A watchdog ends the phase if the exchange hangs (ncclCommAbort,

@@ -36,8 +36,8 @@ def test_bench_gpus_2_launches_two_ranks():
     """... and, after the timed run, C4 across the two ranks through the C
     ABI's exchange lists (c4_cross: over RCCL on a node, here the gloo
     rehearsal through host memory), both the counted and the fixed step."""
-    p = _bench("--gpus", "2", "--dist-backend", "gloo", "--c4-groups",
-               str(G))
+    p = _bench("--full", "--gpus", "2", "--dist-backend", "gloo",
+               "--c4-groups", str(G))
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]  # rank 0 only
@@ -63,6 +63,52 @@ def test_bench_gpus_2_launches_two_ranks():
     # the counted step ships what the round sent, the fixed one every slot
     assert x["counted"]["xchg_bytes_per_round_per_rank"] < \
         x["fixed"]["xchg_bytes_per_round_per_rank"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times its K rounds and prints the line
+    without the secondary measurements; --dump-outputs writes the last
+    round's sampled outputs as float64 arrays, the same at another LocalTick
+    cadence (the inputs are seeded; the dumped fields do not follow the
+    tick clock)."""
+    import numpy as np
+    res, dumps = [], []
+    for te in (1, 2):
+        d = tmp_path / ("dump%d" % te)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+               "--steps", str(K), "--warmup", "2", "--groups", str(G),
+               "--kv-fill", "0", "--tick-every", str(te),
+               "--dump-outputs", str(d)]
+        p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True,
+                           timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [x for x in p.stdout.splitlines() if x.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        res.append(json.loads(lines[0]))
+        dumps.append({f: np.load(str(d / f)) for f in sorted(os.listdir(d))})
+    r = res[0]
+    assert r["steps"] == K and r["ms_per_step"] > 0
+    assert r["counters"]["committed_per_round"] == G
+    assert abs(r["value"] * r["ms_per_step"] * K / 1e3 - G * K) <= 1
+    for key in ("kv_load", "wire", "host_staged", "step_worker",
+                "cpu_baseline", "c4_cross"):
+        assert key not in r, key
+    a, b = dumps
+    assert sorted(a) == ["applied.npy", "counters.npy", "kv.npy",
+                         "read_results.npy", "ready.npy", "replicas.npy"]
+    assert sorted(b) == sorted(a)
+    for f in a:
+        assert a[f].dtype == np.float64 and a[f].ndim == 2, f
+        assert np.array_equal(a[f], b[f]), f
+    # G <= 4096: every group is in the sample; the last round applied one
+    # entry per replica, released one ctx per group and served its 9 reads
+    assert a["replicas.npy"].shape[0] == G * 3
+    assert a["applied.npy"].shape[0] == G * 3
+    assert a["ready.npy"].shape[0] == G
+    assert a["read_results.npy"].shape[0] == G * 9
+    assert a["counters.npy"][0, 0] == G * K and a["counters.npy"][0, -1] == K
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
 
 
 def test_bench_rejects_gpus_unlike_world_size():

@@ -8,11 +8,11 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 o=gpurun_out/${1:-r05_final}
 mkdir -p $o
-tools/gpu_step.sh 400 $o/bench_c3.log python bench.py || exit 1
+tools/gpu_step.sh 400 $o/bench_c3.log python bench.py --full || exit 1
 grep -E '^\{' $o/bench_c3.log > $o/bench_c3.json
 for w in "c2" "c4" "c5 --payload 128" "c5 --payload 1024"; do
   n=$(echo $w | tr -d ' -' | sed 's/payload/_/')
-  tools/gpu_step.sh 300 $o/bench_$n.log python bench.py --workload $w --no-cpu-baseline || exit 1
+  tools/gpu_step.sh 300 $o/bench_$n.log python bench.py --full --workload $w --no-cpu-baseline || exit 1
   grep -E '^\{' $o/bench_$n.log > $o/bench_$n.json
 done
 B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-wire --host-staged 0 --step-worker 0"

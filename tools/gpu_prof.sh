@@ -18,10 +18,10 @@ if [ $tests = 1 ]; then
   grep -q " passed" "$o/pytest_gpu.log" || exit 1
   grep -q "failed\|error" "$o/pytest_gpu.log" && { grep -i "failed\|error" "$o/pytest_gpu.log" | head -20; }
 fi
-tools/gpu_step.sh 400 "$o/bench.log" python bench.py "$@" || exit 1
+tools/gpu_step.sh 400 "$o/bench.log" python bench.py --full "$@" || exit 1
 tail -1 "$o/bench.log" > "$o/bench.json"
 cut -c1-400 "$o/bench.json"
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --tick-every 1 $*"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --tick-every 1 $*"
 tools/gpu_step.sh 300 "$o/trace.log" rocprofv3 --kernel-trace --stats -d "$o/trace" -o run --output-format csv -- $B || exit 1
 tools/gpu_step.sh 200 "$o/fetch.log" rocprofv3 --pmc FETCH_SIZE -d "$o/fetch" -o run --output-format csv -- $B || exit 1
 tools/gpu_step.sh 200 "$o/write.log" rocprofv3 --pmc WRITE_SIZE -d "$o/write" -o run --output-format csv -- $B || exit 1

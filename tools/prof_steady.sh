@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 o=gpurun_out/${1:-r03_head}; shift
 mkdir -p $o
-tools/gpu_step.sh 400 $o/bench.log python bench.py "$@" || exit 1
+tools/gpu_step.sh 400 $o/bench.log python bench.py --full "$@" || exit 1
 tail -1 $o/bench.log > $o/bench.json
 B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-wire --host-staged 0 $*"
 tools/gpu_step.sh 300 $o/trace.log rocprofv3 --kernel-trace --stats -d $o/trace -o run --output-format csv -- $B || exit 1
