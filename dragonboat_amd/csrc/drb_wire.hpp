@@ -157,8 +157,13 @@ DRB_DEV WireMsg wc_next(WireCursor &c, const View &v, const WireArgs &a,
   const uint4 c0 = v.mbox[mbox_ix(v, a.buf, a.from, a.to, k, 0, g)];
   uint4 c1 = make_uint4(0, 0, 0, 0);
   if (c0.x & MF_HAS_C1) c1 = v.mbox[mbox_ix(v, a.buf, a.from, a.to, k, 1, g)];
+  // a record sent before its sender's term changed within the round (or
+  // a pre-vote's) carries its own term, not the header's (rterm)
+  const uint64_t rt = ((c0.x & MF_TERM_OTHER) && v.rterm)
+                          ? v.rterm[rterm_ix(v, a.buf, a.from, a.to, k, g)]
+                          : q_hi(c.meta);
   WireMsg w;
-  w.m = msg_decode(c0, c1, q_hi(c.meta), c.prev_lo, c.prev_hi);
+  w.m = msg_decode(c0, c1, rt, c.prev_lo, c.prev_hi);
   w.shard_id = v.first_shard_id + gid(v, a.from, g);
   c.q++;
   return w;

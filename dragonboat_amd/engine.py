@@ -616,6 +616,8 @@ class Engine:
         """Replaces replica (g, slot)'s KV with the {key: value} dict
         (drb_kv_import, the state machine handed back after a fallback)."""
         n = len(kv)
+        if any(len(k) > 8 for k in kv):  # (the key rows below are 8 B)
+            raise DrbError("drb_kv_import failed with status -5")
         stride = max([len(x) for x in kv.values()] + [1])
         keys = (C.c_uint8 * max(1, 8 * n))()
         vals = (C.c_uint8 * max(1, stride * n))()

@@ -83,15 +83,22 @@ class Pair:
 
     def stage(self, k=1, salt=None, read_index=False, groups=None,
               key_space=256, val_len=4, prop_slot=0, ri_slot=0,
-              ri_replica=0, prop_replica=0):
+              ri_replica=0, prop_replica=0, batch=None):
+        """batch=(counts, ents, pool): a caller-built batch in
+        workload.build_batch's layout (ents [g][k], k = len(ents) // G)
+        staged on both sides in place of the seeded one."""
         salt = self.rounds if salt is None else salt
         pin = ri_in = abi.DRB_NONE
         if self.cpu:  # no client input for groups on the CPU path
             groups = [g for g in (range(self.G) if groups is None else groups)
                       if g not in self.cpu]
+        if batch is not None:
+            counts, ents, pool = batch
+            k = len(ents) // self.G
         if k:
-            counts, ents, pool = workload.build_batch(
-                self.G, k, self.seed, salt, key_space, val_len, groups)
+            if batch is None:
+                counts, ents, pool = workload.build_batch(
+                    self.G, k, self.seed, salt, key_space, val_len, groups)
             self.orc.stage_proposals(counts, k, ents, pool, prop_replica)
             # the engine's staging layout is [g][max_props]
             mp = self.eng.cfg["max_props"]

@@ -125,14 +125,15 @@ class TwoNodes:
     (drb_encode_wire -> drb_ingest_wire); one oracle cluster with every
     replica co-resident is the reference."""
 
-    def __init__(self, G, R=3, seed=0x5EEDD8B0, did=0xD1D, by_slot=False):
+    def __init__(self, G, R=3, seed=0x5EEDD8B0, did=0xD1D, by_slot=False,
+                 **engine_kw):
         from dragonboat_amd import abi
         from dragonboat_amd.engine import Engine
         self.G, self.R, self.seed, self.did = G, R, seed, did
         self.orc = po.Cluster(G, R, seed=seed)
         self.orc.setup_steady(0)
-        self.lead = Engine(num_groups=G, num_replicas=R)
-        self.foll = Engine(num_groups=G, num_replicas=R)
+        self.lead = Engine(num_groups=G, num_replicas=R, **engine_kw)
+        self.foll = Engine(num_groups=G, num_replicas=R, **engine_kw)
         for eng, mine in ((self.lead, {0}), (self.foll, set(range(1, R)))):
             eng.init_steady(term=2, leader_slot=0, seed=seed)
             if by_slot:  # drb_host_slot: one call per slot, no round trip
@@ -148,12 +149,12 @@ class TwoNodes:
         self.rounds = 0
         self.wire_bytes = 0
 
-    def round(self, k=1, tick=False, read_index=False):
+    def round(self, k=1, tick=False, read_index=False, val_len=4):
         from dragonboat_amd import abi, workload
         pin = ri_in = abi.DRB_NONE
         if k:
             counts, ents, pool = workload.build_batch(
-                self.G, k, self.seed, self.rounds, 256, 4, None)
+                self.G, k, self.seed, self.rounds, 256, val_len, None)
             self.orc.stage_proposals(counts, k, ents, pool)
             mp = self.lead.cfg["max_props"]
             eents = (abi.Entry * (self.G * mp))()
