@@ -3,8 +3,9 @@
 hipcc cross-compiles for gfx950 without a GPU; the .so is built in-tree so
 it travels to the GPU box with the repository snapshot.
 
-The step kernel has 72 instantiations (R = 1..8 replicas per group x nine
-kinds, drb_launch.hpp, the lean kernel's two among them).  Each is its own translation unit
+The step kernel has 80 instantiations (R = 1..8 replicas per group x nine
+kinds, drb_launch.hpp, the lean kernel's two among them, and the four LOCAL
+kinds for R = 3 and 5).  Each is its own translation unit
 (drb_step_inst.hip compiled with -DDRB_INST_R / -DDRB_INST_KIND), so the
 objects build in parallel and only the ones whose sources changed rebuild;
 the engine's host code and auxiliary kernels are drb_engine.hip.
@@ -30,7 +31,8 @@ LOCAL_KINDS, LOCAL_R = (9, 10, 11, 12), (3, 5)
 # the headers a step-kernel instantiation includes
 STEP_DEPS = ["drb_step_inst.hip", "drb_step.hpp", "drb_lean.hpp",
              "drb_launch.hpp",
-             "drb_layout.hpp", "drb_msg.hpp", "drb_codec.hpp", "drb_ring.hpp"]
+             "drb_layout.hpp", "drb_msg.hpp", "drb_codec.hpp", "drb_ring.hpp",
+             "drb_snappy.hpp"]
 # the tan record kernels' (drb_tan_inst.hip)
 TAN_DEPS = ["drb_tan_inst.hip", "drb_tan.hpp", "drb_launch.hpp",
             "drb_layout.hpp", "drb_codec.hpp", "drb_ring.hpp"]

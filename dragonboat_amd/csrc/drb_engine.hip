@@ -282,7 +282,7 @@ extern "C" int drb_engine_create(const drb_config *cfg, drb_engine **out) {
   e->bytes = 0;
   e->scratch = nullptr;
   e->scratch_bytes = 0;
-  if (cfg->host_copies > 1) {
+  if (cfg->host_copies > 1 || cfg->entry_compression > 1) {
     delete e;
     return DRB_EINVAL;
   }
@@ -401,6 +401,11 @@ extern "C" int drb_engine_create(const drb_config *cfg, drb_engine **out) {
     rc |= dalloc(e, &v.kv_ovf_next, v.kv_ovf_cap);
     rc |= dalloc(e, &v.kv_ovf_head, R * G);
     rc |= dalloc(e, &v.kv_ovf_used, 1);
+  }
+  v.snappy = cfg->entry_compression;
+  if (v.snappy) {  // the decoded payload's row per replica lane
+    v.D16 = (16 + cfg->kv_val_cap + 15) / 16;
+    rc |= dalloc(e, &v.snap, R * v.D16 * G);
   }
   v.P = cfg->prop_slots;
   v.fwd_props = cfg->forward_proposals ? 1u : 0u;
@@ -562,6 +567,14 @@ extern "C" int drb_engine_destroy(drb_engine *e) {
 
 extern "C" uint64_t drb_engine_device_bytes(const drb_engine *e) {
   return e ? e->bytes : 0;
+}
+
+extern "C" int drb_payload_decode(uint32_t type, const uint8_t *cmd,
+                                  size_t len, uint8_t *out, size_t cap,
+                                  size_t *out_len) {
+  if ((len && !cmd) || (cap && !out) || !out_len) return DRB_EINVAL;
+  const int rc = payload_decode(type, cmd, len, out, cap, out_len);
+  return rc == 0 ? DRB_OK : rc == -3 ? DRB_ERANGE : DRB_EINVAL;
 }
 
 extern "C" void *drb_engine_stream(drb_engine *e) {
@@ -1101,7 +1114,9 @@ __global__ void k_stage_props(View v, uint32_t slot, const uint32_t *counts,
     const uint32_t b0 = en.cmd_len ? cmd[0] : 0u;
     v.props[prop_ix(v, slot, j, 2, g)] = make_uint4(
         en.type, en.cmd_len,
-        prop_fast(en.type, en.client_id, en.series_id, en.cmd_len, b0), 0);
+        prop_fast(en.type, en.client_id, en.series_id, en.cmd_len, b0,
+                  v.snappy),
+        0);
     for (uint32_t c = 0; c < v.C16; ++c) {
       uint32_t w[4] = {0, 0, 0, 0};
       for (uint32_t b = 0; b < 16 && c * 16 + b < en.cmd_len; ++b)
@@ -1201,7 +1216,8 @@ __global__ void k_stage_packed(View v, uint32_t slot, uint32_t type,
     }
     const uint8_t *cmd = pool + off;
     v.props[prop_ix(v, slot, j, 2, g)] = make_uint4(
-        type, len, prop_fast(type, cid, 0, len, len ? cmd[0] : 0u), 0);
+        type, len, prop_fast(type, cid, 0, len, len ? cmd[0] : 0u, v.snappy),
+        0);
     for (uint32_t c = 0; c < v.C16; ++c) {
       uint32_t w[4] = {0, 0, 0, 0};
       for (uint32_t b = 0; b < 16 && c * 16 + b < len; ++b)
@@ -1463,8 +1479,8 @@ __device__ static void gen_kv_lane(const View &v, uint32_t ps, uint32_t k,
     v.props[prop_ix(v, ps, j, 0, lane)] = mk4(r0 | 1, cid);
     v.props[prop_ix(v, ps, j, 1, lane)] = mk4(0, 0);
     v.props[prop_ix(v, ps, j, 2, lane)] = make_uint4(
-        DRB_ENTRY_ENCODED, clen, prop_fast(DRB_ENTRY_ENCODED, cid, 0, clen, 0),
-        0);
+        DRB_ENTRY_ENCODED, clen,
+        prop_fast(DRB_ENTRY_ENCODED, cid, 0, clen, 0, v.snappy), 0);
   }
 }
 
@@ -1855,7 +1871,8 @@ extern "C" int drb_ingest_ex(drb_engine *e, const drb_message *msgs, size_t n,
         pc[1] = mk4h(en.series_id, en.responded_to);
         pc[2] = make_uint4(en.type, en.cmd_len,
                            prop_fast(en.type, en.client_id, en.series_id,
-                                     en.cmd_len, en.cmd_len ? cmd[0] : 0u),
+                                     en.cmd_len, en.cmd_len ? cmd[0] : 0u,
+                                     v.snappy),
                            0);
         if (en.cmd_len) memcpy(&pc[PROP_META], cmd, en.cmd_len);
         for (uint32_t c = 0; c < PROP_META + v.C16; ++c) {
@@ -2194,7 +2211,7 @@ static void launch_step(drb_engine *e, const RoundParams &p0,
   // the EXT instantiation only where its paths can run (drb_step.hpp)
   const bool ext =
       e->v.C16 > 4 || e->v.kv_ool || p0.encode_saves || e->v.quiesce ||
-      e->v.kv_ovf_cap;
+      e->v.kv_ovf_cap || e->v.snappy;
   pl.nrows = nl;
   pf.nrows = nf;
   // one-dimensional grids of the role's slot rows, row-major (block_pos);
@@ -2650,9 +2667,17 @@ __global__ __launch_bounds__(256) void k_apply_results(
     r.series_id = hi64(m1);
     const uint32_t type = m2.z, clen = m2.w;
     r.ignored = r.client_id == 0 ? 1u : 0u;  // an empty no-op entry
-    // KVTest.Update's Result.Value: the payload length (kvtest.go:161)
+    // KVTest.Update's Result.Value: the payload length (kvtest.go:161); a
+    // Snappy entry's is the decoded one, which the apply checked against
+    // the length its block declares
     r.value = r.ignored ? 0
                         : (type == DRB_ENTRY_ENCODED && clen ? clen - 1 : clen);
+    if (v.snappy && !r.ignored && type == DRB_ENTRY_ENCODED && clen &&
+        clen <= v.C16 * 16) {
+      SnapRowsIn<uint4> in(v.ring + ring_ix(v, slot, idx, ENT_META, g), v.G);
+      uint32_t next = 0;
+      if (in.get(0) == 0x02) r.value = snappy_declared(in, clen, &next);
+    }
     r.slot = slot;
     out[pos + k] = r;
   }

@@ -617,7 +617,9 @@ __global__ void k_ing_place(const View v, const uint8_t *s, const DecMsg *dm,
             (uint32_t)en.responded_to, (uint32_t)(en.responded_to >> 32));
         v.props[prop_ix(v, fw, x, 2, g)] = make_uint4(
             en.type, en.cmd_len,
-            prop_fast(en.type, en.client_id, en.series_id, en.cmd_len, b0), 0);
+            prop_fast(en.type, en.client_id, en.series_id, en.cmd_len, b0,
+                      v.snappy),
+            0);
         for (uint32_t cc = 0; cc < v.C16; ++cc) {
           uint32_t w[4] = {0, 0, 0, 0};
           for (uint32_t b = 0; b < 16 && cc * 16 + b < en.cmd_len; ++b)

@@ -276,17 +276,22 @@ constexpr int PROP_META = 3;
 // 969, encoded.go:55-65, kvtest.go:145-162): an application or encoded
 // entry of the NoOP session (SeriesID 0; ClientID 0 only when empty), an
 // encoded Cmd carrying the v0 header byte 0x00 (no compression, no
-// session).  Computed when the proposal is staged; anything else (config
-// change, session management, regular sessions, Snappy) makes the leader
-// fall back before it appends (DRB_FB_ENTRY_TYPE).
+// session) or, with `snappy` (drb_config.entry_compression = 1), 0x02 (a
+// Snappy block, decoded by the apply: drb_snappy.hpp).  Computed when the
+// proposal is staged; anything else (config change, session management,
+// regular sessions, Snappy without the option) makes the leader fall back
+// before it appends (DRB_FB_ENTRY_TYPE).
 __host__ __device__ inline uint32_t prop_fast(uint32_t type, uint64_t client_id,
                                               uint64_t series_id,
                                               uint32_t cmd_len,
-                                              uint32_t first_byte) {
+                                              uint32_t first_byte,
+                                              uint32_t snappy) {
   if (type != 0 /*APPLICATION*/ && type != 2 /*ENCODED*/) return 0;
   if (series_id != 0) return 0;
   if (client_id == 0) return cmd_len == 0;
-  if (type == 2 && (cmd_len == 0 || first_byte != 0)) return 0;
+  if (type == 2 &&
+      (cmd_len == 0 || !(first_byte == 0 || (snappy && first_byte == 2))))
+    return 0;
   return 1;
 }
 constexpr int RTR_CAP = 8;  // ReadyToRead records per replica per round
@@ -446,6 +451,13 @@ struct View {
   // its block index mod ESC_SPLIT), and their counts
   uint32_t *esc_list;               // [2][R][ESC_SPLIT][esc_seg(G)]
   uint32_t *esc_n;                  // [2][R][ESC_SPLIT]
+  // drb_config.entry_compression = 1: Snappy EncodedEntries are applied on
+  // the device.  A replica lane decodes the entry it applies into its row
+  // of snap, [R][D16][G] -- chunks G apart, as a ring entry's Cmd chunks --
+  // of D16 * 16 = roundup16(16 + kv_val_cap) bytes, the longest PBKV the KV
+  // accepts; the row is reused entry after entry (null with the option off)
+  uint32_t snappy, D16;
+  uint4 *snap;
 };
 
 // The escalation list of a row is split so that no one counter takes every
@@ -591,6 +603,10 @@ __host__ __device__ inline uint64_t prop_ix(const View &v, uint32_t ps,
 __host__ __device__ inline uint32_t fwd_ps(const View &v, uint32_t buf,
                                            uint32_t sender) {
   return v.P + buf * v.R + sender;
+}
+__host__ __device__ inline uint64_t snap_ix(const View &v, uint32_t slot,
+                                            uint32_t chunk, uint64_t g) {
+  return ((uint64_t)slot * v.D16 + chunk) * v.G + g;
 }
 __host__ __device__ inline uint64_t rres_ix(const View &v, uint32_t slot,
                                             uint32_t k, uint32_t j,

@@ -20,6 +20,7 @@
 #include "drb_layout.hpp"
 #include "drb_msg.hpp"
 #include "drb_ring.hpp"
+#include "drb_snappy.hpp"
 
 namespace drb {
 
@@ -1679,16 +1680,22 @@ DRB_DEV uint4 mask16(uint4 q, uint32_t n) {
 }
 
 // value bytes [16 c + base, 16 c + base + 16) of an entry's PBKV value at
-// Cmd offset voff: two ring chunks and a byte shift
+// Cmd offset voff: two ring chunks and a byte shift.  `pay`: the payload is
+// a decoded one, voff an offset into the replica's row of v.snap (chunks G
+// apart like the ring's)
 DRB_DEV uint4 value_chunk(const Lane &L, uint64_t index, uint32_t voff,
-                          uint32_t vlen, uint32_t base, uint32_t c) {
+                          uint32_t vlen, uint32_t base, uint32_t c,
+                          const uint4 *pay = nullptr) {
   const View &v = *L.v;
   const uint32_t o = voff + base + 16 * c;  // Cmd byte offset
   const uint32_t q = o >> 4;
-  const uint4 q0 = v.ring[ring_ix(v, L.slot, index, ENT_META + q, L.g)];
-  const uint4 q1 = q + 1 < v.C16
-                       ? v.ring[ring_ix(v, L.slot, index, ENT_META + q + 1, L.g)]
-                       : make_uint4(0, 0, 0, 0);
+  const uint4 *src =
+      pay ? pay : v.ring + ring_ix(v, L.slot, index, ENT_META, L.g);
+  const uint32_t nq = pay ? v.D16 : v.C16;
+  // (a chunk past the payload's rows is asked for only when `have` is 0)
+  const uint4 q0 = q < nq ? src[(uint64_t)q * v.G] : make_uint4(0, 0, 0, 0);
+  const uint4 q1 =
+      q + 1 < nq ? src[(uint64_t)(q + 1) * v.G] : make_uint4(0, 0, 0, 0);
   const uint32_t have = vlen > base + 16 * c ? vlen - base - 16 * c : 0;
   return mask16(extract16(q0, q1, o & 15), have > 16 ? 16 : have);
 }
@@ -1700,7 +1707,8 @@ DRB_DEV uint4 value_chunk(const Lane &L, uint64_t index, uint32_t voff,
 DRB_DEV bool put_value_long(const View &v, uint32_t slot,
                                             uint64_t g, uint64_t index,
                                             uint4 *sl, bool hit,
-                                            uint32_t voff, uint32_t vlen) {
+                                            uint32_t voff, uint32_t vlen,
+                                            const uint4 *pay = nullptr) {
   Lane L;
   L.v = &v;
   L.slot = slot;
@@ -1717,10 +1725,10 @@ DRB_DEV bool put_value_long(const View &v, uint32_t slot,
     }
     uint4 *dst = v.kv_pool + (uint64_t)blk * v.VB;
     for (uint32_t c = 0; c * 16 < vlen; ++c)
-      dst[c] = value_chunk(L, index, voff, vlen, 0, c);
+      dst[c] = value_chunk(L, index, voff, vlen, 0, c, pay);
   } else {
     for (uint32_t c = 1; c < v.KVW; ++c)
-      sl[c] = value_chunk(L, index, voff, vlen, 4, c - 1);
+      sl[c] = value_chunk(L, index, voff, vlen, 4, c - 1, pay);
   }
   return true;
 }
@@ -1758,6 +1766,21 @@ DRB_DEV uint4 *kv_ovf_walk(const View &v, uint32_t slot, uint64_t g,
   return v.kv_ovf + (uint64_t)nb * 4 * v.KVW;
 }
 
+// A Snappy EncodedEntry's block (drb_snappy.hpp) from the entry's Cmd chunks
+// `cmd` into the replica's row `row` of at most cap bytes, both with chunks
+// G apart.  Returns the decoded length, 0 for a block that is corrupt or
+// declares more than cap.  Not inlined: the byte loop and the chunks it
+// keeps in registers stay out of the step kernel's live ranges.
+static __device__ __noinline__ uint32_t snappy_to_row(const uint4 *cmd,
+                                                      uint4 *row, uint64_t G,
+                                                      uint32_t clen,
+                                                      uint32_t cap) {
+  SnapRowsIn<uint4> in(cmd, G);
+  SnapRowsOut<uint4> out(row, G);
+  uint32_t n = 0;
+  return snappy_decode(in, clen, out, cap, &n) ? 0u : n;
+}
+
 // handleEntry (statemachine.go:935-969) -> update (1057-1103) ->
 // GetPayload (encoded.go:55-65) -> KVTest.Update (kvtest.go:145-162).
 // Returns: 0 noop applied, 1 KV updated, -1 not on the fast path, -2 the
@@ -1792,12 +1815,35 @@ DRB_DEV int apply_entry(const Lane &L, Rep<R> &r, uint64_t index) {
   if (v.C16 > 2) cmd.c2 = v.ring[ring_ix(v, L.slot, index, ENT_META + 2, L.g)];
   if (v.C16 > 3) cmd.c3 = v.ring[ring_ix(v, L.slot, index, ENT_META + 3, L.g)];
   uint32_t off = 0, plen = clen;
+  // EXT: a decoded Snappy payload's chunks (the replica's row of v.snap)
+  const uint4 *pay = nullptr;
   if (type == DRB_ENTRY_ENCODED) {
     if (clen == 0) return -1;
     uint32_t h = cmd_byte(cmd, 0);
-    if ((h & 0xf0) != 0 || (h & 0x0e) != 0 || (h & 1)) return -1;
-    off = 1;
-    plen = clen - 1;
+    bool snappy = false;
+    if constexpr (EXT) snappy = v.snappy && h == 0x02;
+    if (snappy) {
+      // getDecodedPayload (encoded.go:127-160): the whole block is decoded
+      // into the row before the KV is touched, then parsed and applied from
+      // there as an uncompressed payload would be from the window.  A
+      // corrupt block, or one that declares more than the row holds (the
+      // largest PBKV the KV accepts), is not on the fast path.
+      if (clen > v.C16 * 16) return -1;
+      uint4 *row = v.snap + snap_ix(v, L.slot, 0, L.g);
+      plen = snappy_to_row(v.ring + ring_ix(v, L.slot, index, ENT_META, L.g),
+                           row, v.G, clen, v.D16 * 16);
+      if (plen == 0) return -1;
+      pay = row;
+      cmd.c0 = row[0];
+      cmd.c1 = cmd.c2 = cmd.c3 = make_uint4(0, 0, 0, 0);
+      if (v.D16 > 1) cmd.c1 = row[v.G];
+      if (v.D16 > 2) cmd.c2 = row[2 * v.G];
+      if (v.D16 > 3) cmd.c3 = row[3 * v.G];
+    } else {
+      if ((h & 0xf0) != 0 || (h & 0x0e) != 0 || (h & 1)) return -1;
+      off = 1;
+      plen = clen - 1;
+    }
   } else if (type != DRB_ENTRY_APPLICATION) {
     return -1;
   }
@@ -1841,7 +1887,7 @@ DRB_DEV int apply_entry(const Lane &L, Rep<R> &r, uint64_t index) {
   // the value's first 4 bytes (kept in the slot header word either way)
   const uint32_t w0 =
       (!EXT || voff + 4 <= 64 ? cmd_u32_at(cmd, voff)
-                              : value_chunk(L, index, voff, vlen, 0, 0).x) &
+                              : value_chunk(L, index, voff, vlen, 0, 0, pay).x) &
       byte_mask(vlen);
   // open-addressing upsert into this replica's table: DRB_PROBE_W slots
   // are loaded per step (one memory round trip), then resolved in order
@@ -1882,7 +1928,7 @@ DRB_DEV int apply_entry(const Lane &L, Rep<R> &r, uint64_t index) {
           sl[c] = make_uint4(wv[0], wv[1], wv[2], wv[3]);
         }
       } else if (!put_value_long(v, L.slot, L.g, index, sl, hit, voff,
-                                 vlen)) {
+                                 vlen, pay)) {
         return -2;  // value pool exhausted
       }
       sl[0] = make_uint4((uint32_t)key8, (uint32_t)(key8 >> 32),
@@ -1897,7 +1943,8 @@ DRB_DEV int apply_entry(const Lane &L, Rep<R> &r, uint64_t index) {
   if (EXT && v.kv_ovf_head) {  // the table is full: the overflow chain
     bool hit = false;
     uint4 *sl = kv_ovf_walk(v, L.slot, L.g, key8, klen, true, hit);
-    if (sl && put_value_long(v, L.slot, L.g, index, sl, hit, voff, vlen)) {
+    if (sl &&
+        put_value_long(v, L.slot, L.g, index, sl, hit, voff, vlen, pay)) {
       sl[0] = make_uint4((uint32_t)key8, (uint32_t)(key8 >> 32),
                          (1u << 31) | (vlen << 8) | klen, w0);
       r.kv_added++;

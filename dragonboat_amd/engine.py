@@ -151,6 +151,7 @@ SIGNATURES = {
     "drb_worker_wait": (C.c_int, [P, C.POINTER(abi.WorkerBufs)]),
     "drb_host_alloc": (C.c_int, [P, SZ, C.POINTER(P)]),
     "drb_host_free": (C.c_int, [P, P]),
+    "drb_payload_decode": (C.c_int, [U32, PU8, SZ, PU8, SZ, C.POINTER(SZ)]),
 }
 
 
@@ -188,6 +189,17 @@ def _u8(b):
     return (C.c_uint8 * max(1, len(b))).from_buffer_copy(bytes(b) or b"\0")
 
 
+def payload_decode(type, cmd, cap):
+    """GetPayload of an entry's Cmd on the host (drb_payload_decode): the
+    payload of at most `cap` bytes, a Snappy block decompressed.  Needs no
+    engine and no device; DrbError for a Cmd the reference rejects."""
+    out = (C.c_uint8 * max(1, cap))()
+    n = SZ(0)
+    _ck(lib().drb_payload_decode(type, _u8(cmd), len(cmd), out, cap,
+                                 C.byref(n)), "drb_payload_decode")
+    return bytes(out[:n.value])
+
+
 DEFAULTS = dict(num_groups=1, first_shard_id=1, num_replicas=3, window=32,
                 cmd_cap=32, max_props=4, prop_slots=2, ri_slots=2,
                 mailbox=16, kv_slots=512, kv_val_cap=4, election_rtt=10,
@@ -198,7 +210,7 @@ DEFAULTS = dict(num_groups=1, first_shard_id=1, num_replicas=3, window=32,
                 tan_multiplexed=0, pre_vote=0, max_reads_per_ctx=0,
                 kv_overflow_buckets=0, forward_proposals=0,
                 nonvoting_slots=0, witness_slots=0, host_copies=0,
-                no_lean=0)
+                no_lean=0, entry_compression=0)
 
 
 class Engine:
@@ -223,7 +235,7 @@ class Engine:
                    cfg["max_reads_per_ctx"], cfg["kv_overflow_buckets"],
                    cfg["forward_proposals"], cfg["nonvoting_slots"],
                    cfg["witness_slots"], cfg["host_copies"],
-                   cfg["no_lean"])
+                   cfg["no_lean"], cfg["entry_compression"])
         h = P()
         _ck(lib().drb_engine_create(C.byref(c), C.byref(h)),
             "drb_engine_create")

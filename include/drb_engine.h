@@ -142,7 +142,10 @@ enum drb_fallback_reason {
   DRB_FB_MESSAGE_TYPE = 2,      /* message type handled only on the CPU path */
   DRB_FB_ELECTION = 3,          /* raft.go:602 election timeout */
   DRB_FB_CHECK_QUORUM = 4,      /* raft.go:1785 leader lost quorum */
-  DRB_FB_ENTRY_TYPE = 5,        /* config change / session / compressed entry */
+  DRB_FB_ENTRY_TYPE = 5,        /* config change / session entry; a Snappy
+                                 * entry without entry_compression, or one
+                                 * whose block is corrupt or decodes to more
+                                 * than the KV accepts */
   DRB_FB_CAPACITY = 6,          /* window / mailbox / readIndex capacity */
   DRB_FB_ROLE = 7,              /* candidate / non-voting / witness */
   DRB_FB_SNAPSHOT = 9,          /* a remote in the Snapshot state
@@ -289,7 +292,9 @@ typedef struct drb_config {
   uint32_t num_replicas;     /* R, 1..DRB_MAX_REPLICAS; replica IDs 1..R */
   uint32_t window;           /* W resident entries per replica (power of 2) */
   uint32_t cmd_cap;          /* max Cmd bytes per resident entry (mult. of
-                              * 16, <= 1040) */
+                              * 16, <= 1040); with entry_compression the
+                              * Cmd as proposed (header byte + Snappy block):
+                              * its decoded payload may be longer */
   uint32_t max_props;        /* max proposals per group per round */
   uint32_t prop_slots;       /* staged proposal batches */
   uint32_t ri_slots;         /* staged ReadIndex batches */
@@ -427,6 +432,18 @@ typedef struct drb_config {
    * kernel; 0: the heartbeat-only rounds of quiet groups go through the
    * lean kernel first (drb_lean.hpp; for A/B measurements) */
   uint32_t no_lean;
+  /* Config.EntryCompressionType (config.CompressionType: 0 NoCompression,
+   * 1 Snappy).  1: an EncodedEntry whose header byte is 0x02 (what
+   * rsm.GetEncoded makes of a proposal on the host) is appended, replicated
+   * and saved as the opaque bytes it is, and the apply decodes its Snappy
+   * block on the device (drb_snappy.hpp) into a per-replica row of
+   * roundup16(16 + kv_val_cap) bytes -- R x G rows, counted by
+   * drb_engine_device_bytes -- before the KV update.  A block that is
+   * corrupt, or declares more than that row, stops the replica's apply at
+   * the entry (DRB_F_APPLY_STOPPED, DRB_FB_ENTRY_TYPE) with the KV
+   * untouched.  0: such entries are not on the fast path (the leader falls
+   * back before appending, DRB_FB_ENTRY_TYPE).  Other values: DRB_EINVAL. */
+  uint32_t entry_compression;
 } drb_config;
 
 /* One step round (engine.processSteps, engine.go:1304). */
@@ -1217,7 +1234,8 @@ int drb_exchange_mark(drb_engine *e);
  * node.ApplyUpdate -> pendingProposals.applied (node.go:243-257,
  * request.go:1041-1045; rsm handleEntry statemachine.go:935-969): per
  * entry its Key / ClientID / SeriesID and sm.Result.Value, which KVTest
- * sets to the length of the update's Cmd payload (kvtest.go:161).  Groups
+ * sets to the length of the update's Cmd payload (kvtest.go:161; of a
+ * Snappy entry, the decoded payload).  Groups
  * [first_group, first_group + n_groups), sorted by (group, index); *n_out
  * is the count (DRB_ERANGE if more than cap).  Replicas handed to the CPU
  * path report nothing, except those whose apply stopped
@@ -1375,6 +1393,18 @@ int drb_ingest_buffer(drb_engine *e, size_t cap, uint8_t **buf);
  * returning, so a buffer may be refilled as soon as the call returns. */
 int drb_ingest_buffer_alloc(drb_engine *e, size_t cap, uint8_t **buf);
 int drb_ingest_buffer_free(drb_engine *e, uint8_t *buf);
+
+/* GetPayload (internal/rsm/encoded.go:55-66) on the host, by the code the
+ * device's apply runs (drb_snappy.hpp): the payload of an entry's Cmd --
+ * the Cmd itself for an application or config change entry, the bytes after
+ * the header for an EncodedEntry, decompressed when the header says Snappy
+ * -- into out[0, cap), its length in *out_len.  DRB_OK; DRB_EINVAL for a
+ * null argument and for what the reference panics on or returns an error
+ * for (an unknown type or header, an empty encoded Cmd, a corrupt block);
+ * DRB_ERANGE for a payload, or a block's declared length, above cap.
+ * Needs no engine and no device. */
+int drb_payload_decode(uint32_t type, const uint8_t *cmd, size_t len,
+                       uint8_t *out, size_t cap, size_t *out_len);
 
 #ifdef __cplusplus
 }
