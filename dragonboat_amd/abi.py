@@ -49,6 +49,7 @@ F_APPLY_STOPPED = 8
 
 FB = dict(NONE=0, TERM_MISMATCH=1, MESSAGE_TYPE=2, ELECTION=3,
           CHECK_QUORUM=4, ENTRY_TYPE=5, CAPACITY=6, ROLE=7, SNAPSHOT=9,
+          RECOVERY=10,
           ERR_LOG_RANGE=100, ERR_COMMIT=101, ERR_APPEND=103, ERR_APPLY=104,
           ERR_READINDEX=105, ERR_TRANSFER=106, ERR_PROPOSE=107)
 FB_NAME = {v: k for k, v in FB.items()}
@@ -228,6 +229,56 @@ class TanState(C.Structure):
     """drb_tan_state: a replica's tan writer position."""
     _fields_ = [("offset", C.c_uint64), ("log", C.c_uint32),
                 ("state_stored", C.c_uint32)]
+
+
+# drb_tan_outcome: how drb_tan_scan's file ended
+TAN_EOF, TAN_ZEROED, TAN_INVALID, TAN_CRC, TAN_UNEXPECTED_EOF, \
+    TAN_MALFORMED = range(6)
+TAN_OUTCOME_NAME = ["EOF", "ZEROED", "INVALID", "CRC", "UNEXPECTED_EOF",
+                    "MALFORMED"]
+
+# drb_recover_code: a replica's status after drb_recover_tan
+REC_OK, REC_TAIL_CUT, REC_EMPTY, REC_CORRUPT, REC_MISMATCH, REC_GAP, \
+    REC_ENTRY_TYPE, REC_CAPACITY, REC_APPLY_STOPPED, REC_SNAPSHOT = range(10)
+REC_NAME = ["OK", "TAIL_CUT", "EMPTY", "CORRUPT", "MISMATCH", "GAP",
+            "ENTRY_TYPE", "CAPACITY", "APPLY_STOPPED", "SNAPSHOT"]
+
+
+class TanScanRec(C.Structure):
+    """drb_tan_scan_rec: one record of a tan log file."""
+    _fields_ = [("offset", C.c_uint64), ("end", C.c_uint64),
+                ("shard_id", C.c_uint64), ("replica_id", C.c_uint64),
+                ("term", C.c_uint64), ("vote", C.c_uint64),
+                ("commit", C.c_uint64), ("first_index", C.c_uint64),
+                ("last_index", C.c_uint64), ("has_state", C.c_uint32),
+                ("n_entries", C.c_uint32)]
+
+
+class TanFile(C.Structure):
+    """drb_tan_file: one log file of one replica in drb_recover_in.bytes."""
+    _fields_ = [("group", C.c_uint64), ("slot", C.c_uint32),
+                ("log", C.c_uint32), ("off", C.c_uint64), ("len", C.c_uint64)]
+
+
+class RecoverIn(C.Structure):
+    """drb_recover_in."""
+    _fields_ = [("first_group", C.c_uint64), ("n_groups", C.c_uint64),
+                ("bytes", C.c_void_p), ("n_bytes", C.c_size_t),
+                ("files", C.POINTER(TanFile)), ("n_files", C.c_size_t),
+                ("base_index", C.c_uint64), ("base_term", C.c_uint64),
+                ("seed", C.c_uint64)]
+
+
+class RecoverStatus(C.Structure):
+    """drb_recover_status: what drb_recover_tan did with one replica."""
+    _fields_ = [("status", C.c_uint32), ("log", C.c_uint32),
+                ("offset", C.c_uint64), ("records", C.c_uint64),
+                ("entries", C.c_uint64), ("term", C.c_uint64),
+                ("vote", C.c_uint64), ("commit", C.c_uint64),
+                ("last_index", C.c_uint64), ("applied", C.c_uint64)]
+
+    def to_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 class TanLog(C.Structure):

@@ -8,7 +8,9 @@ kinds, drb_launch.hpp, the lean kernel's two among them, and the four LOCAL
 kinds for R = 3 and 5).  Each is its own translation unit
 (drb_step_inst.hip compiled with -DDRB_INST_R / -DDRB_INST_KIND), so the
 objects build in parallel and only the ones whose sources changed rebuild;
-the engine's host code and auxiliary kernels are drb_engine.hip.
+the engine's host code and auxiliary kernels are drb_engine.hip, the tan
+record kernels (drb_tan_inst.hip, twice) and the recovery kernels
+(drb_recover_inst.hip) units of their own.
 """
 import hashlib
 import os
@@ -33,6 +35,10 @@ STEP_DEPS = ["drb_step_inst.hip", "drb_step.hpp", "drb_lean.hpp",
              "drb_launch.hpp",
              "drb_layout.hpp", "drb_msg.hpp", "drb_codec.hpp", "drb_ring.hpp",
              "drb_snappy.hpp"]
+# the recovery kernels' (drb_recover_inst.hip): the step kernel's headers
+# (apply_entry) and the tan read path
+RECOVER_DEPS = STEP_DEPS[1:] + ["drb_recover_inst.hip", "drb_recover.hpp",
+                                "drb_tanread.hpp"]
 # the tan record kernels' (drb_tan_inst.hip)
 TAN_DEPS = ["drb_tan_inst.hip", "drb_tan.hpp", "drb_launch.hpp",
             "drb_layout.hpp", "drb_codec.hpp", "drb_ring.hpp"]
@@ -52,7 +58,9 @@ def _units(defines):
     """(object name, source, extra defines, dependencies) of every TU."""
     step_deps = [os.path.join(CSRC, f) for f in STEP_DEPS] + [_inc()]
     tan_deps = [os.path.join(CSRC, f) for f in TAN_DEPS] + [_inc()]
+    rec_deps = [os.path.join(CSRC, f) for f in RECOVER_DEPS] + [_inc()]
     units = [("drb_engine.o", "drb_engine.hip", [], _deps()),
+             ("recover.o", "drb_recover_inst.hip", [], rec_deps),
              ("tan_write.o", "drb_tan_inst.hip", ["DRB_TAN_KERNELS=2"],
               tan_deps),
              ("tan_select.o", "drb_tan_inst.hip", ["DRB_TAN_KERNELS=1"],

@@ -109,6 +109,9 @@ struct drb_engine {
   // drb_plane_counts has read the plane summaries (xrows): the rounds clear
   // them from then on
   bool xrows_used = false;
+  // drb_recover_tan: the groups a call has already taken (a second recovery
+  // of a group would apply its log into the KV again)
+  std::vector<bool> recovered;
 };
 
 static void wire_free(drb_engine *e);
@@ -4144,6 +4147,195 @@ extern "C" int drb_tan_buffers(drb_engine *e, void **bytes, void **recs) {
   *bytes = e->v.save_buf;
   *recs = e->v.tan_rec;
   return DRB_OK;
+}
+
+// ---------------------------------------------------------------- restart
+#include "drb_recover.hpp"
+
+extern "C" int drb_tan_scan(const uint8_t *log, size_t len,
+                            drb_tan_scan_rec *out, size_t cap, size_t *n,
+                            int *outcome, uint64_t *valid_end) {
+  if ((len && !log) || (cap && !out) || !n || !outcome || !valid_end)
+    return DRB_EINVAL;
+  const TanFile<TanFlatIn> f{TanFlatIn{log}, 0, len};
+  TanWalk w;
+  size_t k = 0;
+  uint64_t vend = 0;
+  int oc;
+  for (;;) {
+    TrScanRec r;
+    oc = tr_scan_record(f, w, r);
+    if (oc != TR_REC) break;
+    if (k < cap) {
+      drb_tan_scan_rec &o = out[k];
+      o.offset = r.offset;
+      o.end = r.end;
+      o.shard_id = r.shard_id;
+      o.replica_id = r.replica_id;
+      o.term = r.term;
+      o.vote = r.vote;
+      o.commit = r.commit;
+      o.first_index = r.first_index;
+      o.last_index = r.last_index;
+      o.has_state = r.has_state;
+      o.n_entries = r.n_entries;
+    }
+    vend = r.end;
+    k++;
+  }
+  *n = k;
+  *outcome = oc;  // TR_* are DRB_TAN_*'s values
+  *valid_end = vend;
+  return DRB_OK;
+}
+static_assert(TR_EOF == DRB_TAN_EOF && TR_ZEROED == DRB_TAN_ZEROED &&
+                  TR_INVALID == DRB_TAN_INVALID && TR_CRC == DRB_TAN_CRC &&
+                  TR_UNEXPECTED_EOF == DRB_TAN_UNEXPECTED_EOF &&
+                  TR_MALFORMED == DRB_TAN_MALFORMED,
+              "drb_tanread.hpp outcomes");
+static_assert(TRS_OK == DRB_REC_OK && TRS_TAIL_CUT == DRB_REC_TAIL_CUT &&
+                  TRS_EMPTY == DRB_REC_EMPTY && TRS_CORRUPT == DRB_REC_CORRUPT &&
+                  TRS_MISMATCH == DRB_REC_MISMATCH && TRS_GAP == DRB_REC_GAP &&
+                  TRS_ENTRY_TYPE == DRB_REC_ENTRY_TYPE &&
+                  TRS_CAPACITY == DRB_REC_CAPACITY &&
+                  TRS_APPLY_STOPPED == DRB_REC_APPLY_STOPPED &&
+                  TRS_SNAPSHOT == DRB_REC_SNAPSHOT,
+              "drb_tanread.hpp statuses");
+
+// the upload's piece: the copy stream takes the log bytes in pieces, so a
+// pageable source is staged piece by piece while the one before it travels
+static const size_t kRecoverPiece = 64ull << 20;
+
+extern "C" int drb_recover_tan(drb_engine *e, const drb_recover_in *in,
+                               drb_recover_status *st) {
+  if (!e || !in || !st) return DRB_EINVAL;
+  if (e->round != 0 || e->v.tan_mux || e->v.place_world > 1) return DRB_EINVAL;
+  if ((in->n_bytes && !in->bytes) || (in->n_files && !in->files))
+    return DRB_EINVAL;
+  if (check_range(e, in->first_group, in->n_groups)) return DRB_ERANGE;
+  if (in->n_groups == 0) return DRB_OK;
+  if (in->n_files > 0xfffffffeull) return DRB_ERANGE;
+  if (e->recovered.empty()) e->recovered.assign(e->cfg.num_groups, false);
+  for (uint64_t gi = 0; gi < in->n_groups; ++gi)
+    if (e->recovered[in->first_group + gi]) return DRB_EINVAL;
+  const View &v = e->v;
+  const uint64_t NR = in->n_groups * v.R;
+  // the file table by replica (a stable counting sort keeps the log order)
+  std::vector<uint32_t> first(NR + 1, 0);
+  auto rep_of = [&](const drb_tan_file &f) {
+    return (uint64_t)f.slot * in->n_groups + (f.group - in->first_group);
+  };
+  for (size_t i = 0; i < in->n_files; ++i) {
+    const drb_tan_file &f = in->files[i];
+    if (f.group < in->first_group || f.group - in->first_group >= in->n_groups ||
+        f.slot >= v.R || f.off > in->n_bytes || f.len > in->n_bytes - f.off)
+      return DRB_ERANGE;
+    first[rep_of(f) + 1]++;
+  }
+  for (uint64_t q = 0; q < NR; ++q) first[q + 1] += first[q];
+  std::vector<RecFile> files(std::max<size_t>(in->n_files, 1));
+  {
+    std::vector<uint32_t> at(first.begin(), first.end() - 1);
+    for (size_t i = 0; i < in->n_files; ++i) {
+      const drb_tan_file &f = in->files[i];
+      const uint64_t q = rep_of(f);
+      const uint32_t k = at[q]++;
+      if (k > first[q] && files[k - 1].log >= f.log) return DRB_EINVAL;
+      files[k] = RecFile{f.off, f.len, f.log, 0};
+    }
+  }
+  uint8_t *dbytes = nullptr;
+  RecFile *dfiles = nullptr;
+  uint32_t *dfirst = nullptr;
+  TrPlan *dplans = nullptr;
+  drb_recover_status *dst = nullptr;
+  auto release = [&]() {
+    (void)hipFree(dbytes);
+    (void)hipFree(dfiles);
+    (void)hipFree(dfirst);
+    (void)hipFree(dplans);
+    (void)hipFree(dst);
+  };
+  if (hipMalloc((void **)&dbytes, in->n_bytes + 16) != hipSuccess ||
+      hipMalloc((void **)&dfiles, files.size() * sizeof(RecFile)) !=
+          hipSuccess ||
+      hipMalloc((void **)&dfirst, first.size() * sizeof(uint32_t)) !=
+          hipSuccess ||
+      hipMalloc((void **)&dplans, NR * sizeof(TrPlan)) != hipSuccess ||
+      hipMalloc((void **)&dst, NR * sizeof(drb_recover_status)) !=
+          hipSuccess) {
+    release();
+    return DRB_ENOMEM;
+  }
+  int rc = DRB_OK;
+  // DRB_RECOVER_TIMING=1 (tools/measure_recover.py): device-event times of
+  // the upload and of each pass, one line on stderr
+  const char *tenv = getenv("DRB_RECOVER_TIMING");
+  const bool timing = tenv && tenv[0] == '1';
+  hipEvent_t tev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (timing)
+    for (auto &ev : tev)
+      if (hipEventCreate(&ev) != hipSuccess) {
+        release();
+        return DRB_EDEVICE;
+      }
+  auto run = [&]() -> int {
+    if (timing) HIPCHK(hipEventRecord(tev[0], e->stream_h2d));
+    for (size_t o = 0; o < in->n_bytes; o += kRecoverPiece)
+      HIPCHK(hipMemcpyAsync(dbytes + o, in->bytes + o,
+                            std::min(kRecoverPiece, in->n_bytes - o),
+                            hipMemcpyHostToDevice, e->stream_h2d));
+    HIPCHK(hipMemcpyAsync(dfiles, files.data(), files.size() * sizeof(RecFile),
+                          hipMemcpyHostToDevice, e->stream_h2d));
+    HIPCHK(hipMemcpyAsync(dfirst, first.data(), first.size() * sizeof(uint32_t),
+                          hipMemcpyHostToDevice, e->stream_h2d));
+    if (timing) HIPCHK(hipEventRecord(tev[1], e->stream_h2d));
+    HIPCHK(hipEventRecord(e->ev_staged, e->stream_h2d));
+    HIPCHK(hipStreamWaitEvent(e->stream, e->ev_staged, 0));
+    RecParams p;
+    p.first_group = in->first_group;
+    p.n_groups = in->n_groups;
+    p.bytes = dbytes;
+    p.files = dfiles;
+    p.rep_first = dfirst;
+    p.base_index = in->base_index;
+    p.base_term = in->base_term;
+    p.seed = in->seed;
+    p.qs_base = e->ticks;
+    p.plans = dplans;
+    p.st = dst;
+    const unsigned blocks = (unsigned)((NR + REC_BLOCK - 1) / REC_BLOCK);
+    if (timing) HIPCHK(hipEventRecord(tev[2], e->stream));
+    recover_launch_check(v, p, blocks, e->stream);
+    HIPCHK(hipGetLastError());
+    if (timing) HIPCHK(hipEventRecord(tev[3], e->stream));
+    recover_launch_place(v, p, blocks, e->stream);
+    HIPCHK(hipGetLastError());
+    if (timing) HIPCHK(hipEventRecord(tev[4], e->stream));
+    HIPCHK(hipMemcpyAsync(st, dst, NR * sizeof(drb_recover_status),
+                          hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (timing) {
+      float up = 0, p1 = 0, p2 = 0;
+      HIPCHK(hipEventElapsedTime(&up, tev[0], tev[1]));
+      HIPCHK(hipEventElapsedTime(&p1, tev[2], tev[3]));
+      HIPCHK(hipEventElapsedTime(&p2, tev[3], tev[4]));
+      fprintf(stderr,
+              "drb_recover_tan: bytes=%zu upload_ms=%.3f check_ms=%.3f "
+              "place_ms=%.3f\n",
+              in->n_bytes, up, p1, p2);
+    }
+    return DRB_OK;
+  };
+  rc = run();
+  if (rc) (void)hipStreamSynchronize(e->stream_h2d);
+  if (timing)
+    for (auto &ev : tev) (void)hipEventDestroy(ev);
+  release();
+  if (rc) return rc;
+  for (uint64_t gi = 0; gi < in->n_groups; ++gi)
+    e->recovered[in->first_group + gi] = true;
+  return refresh_roles(e);
 }
 
 // ------------------------------------------------ batched round outputs

@@ -152,6 +152,10 @@ SIGNATURES = {
     "drb_host_alloc": (C.c_int, [P, SZ, C.POINTER(P)]),
     "drb_host_free": (C.c_int, [P, P]),
     "drb_payload_decode": (C.c_int, [U32, PU8, SZ, PU8, SZ, C.POINTER(SZ)]),
+    "drb_tan_scan": (C.c_int, [PU8, SZ, C.POINTER(abi.TanScanRec), SZ,
+                               C.POINTER(SZ), C.POINTER(C.c_int), PU64]),
+    "drb_recover_tan": (C.c_int, [P, C.POINTER(abi.RecoverIn),
+                                  C.POINTER(abi.RecoverStatus)]),
 }
 
 
@@ -198,6 +202,27 @@ def payload_decode(type, cmd, cap):
     _ck(lib().drb_payload_decode(type, _u8(cmd), len(cmd), out, cap,
                                  C.byref(n)), "drb_payload_decode")
     return bytes(out[:n.value])
+
+
+def tan_scan(data, cap=None):
+    """The records of one tan log file on the host (drb_tan_scan): (outcome,
+    valid_end, [record dicts]) -- outcome one of abi.TAN_*, valid_end the
+    offset after the last good record, at most `cap` records (default: all).
+    Needs no engine and no device."""
+    data = bytes(data)
+    n, oc, vend = SZ(0), C.c_int(0), U64(0)
+    buf = _u8(data)
+    want = 64 if cap is None else cap
+    while True:
+        out = (abi.TanScanRec * max(1, want))()
+        _ck(lib().drb_tan_scan(buf, len(data), out, want, C.byref(n),
+                               C.byref(oc), C.byref(vend)), "drb_tan_scan")
+        if cap is not None or n.value <= want:
+            break
+        want = n.value
+    recs = [{f: getattr(out[i], f) for f, _ in abi.TanScanRec._fields_}
+            for i in range(min(n.value, want))]
+    return oc.value, vend.value, recs
 
 
 DEFAULTS = dict(num_groups=1, first_shard_id=1, num_replicas=3, window=32,
@@ -687,6 +712,29 @@ class Engine:
     def tan_set(self, g, slot, offset, log, state_stored):
         st = abi.TanState(offset, log, int(bool(state_stored)))
         _ck(lib().drb_tan_set(self.h, g, slot, C.byref(st)), "drb_tan_set")
+
+    def recover_tan(self, files, base_index, base_term, seed, first_group=0,
+                    n_groups=None):
+        """drb_recover_tan: the replicas of groups [first_group, first_group
+        + n_groups) restart from their tan logs.  files: {(group, slot):
+        [(log number, bytes), ...] in log order}.  Returns {(group, slot):
+        abi.RecoverStatus} for every replica of the range."""
+        n_groups = self.G - first_group if n_groups is None else n_groups
+        blob, table = bytearray(), []
+        for (g, s), logs in sorted(files.items()):
+            for lg, data in logs:
+                table.append(abi.TanFile(g, s, lg, len(blob), len(data)))
+                blob += data
+        arr = (abi.TanFile * max(1, len(table)))(*table)
+        buf = _u8(blob)
+        rin = abi.RecoverIn(first_group, n_groups, C.cast(buf, C.c_void_p),
+                            len(blob), arr, len(table), base_index, base_term,
+                            seed)
+        st = (abi.RecoverStatus * max(1, n_groups * self.R))()
+        _ck(lib().drb_recover_tan(self.h, C.byref(rin), st),
+            "drb_recover_tan")
+        return {(first_group + gi, s): st[gi * self.R + s]
+                for gi in range(n_groups) for s in range(self.R)}
 
     def export_save_records(self, g, slot):
         """save_batched: [(batch id, record value, crc32)] of one replica's

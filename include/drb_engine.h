@@ -150,6 +150,8 @@ enum drb_fallback_reason {
   DRB_FB_ROLE = 7,              /* candidate / non-voting / witness */
   DRB_FB_SNAPSHOT = 9,          /* a remote in the Snapshot state
                                  * (remote.go:54-59, 128-141) */
+  DRB_FB_RECOVERY = 10,         /* drb_recover_tan refused the replica's tan
+                                 * logs (its drb_recover_status says why) */
   DRB_ERR_LOG_RANGE = 100,      /* internal invariant: a read below the
                                  * resident window the pre-pass did not
                                  * predict (it falls back with CAPACITY) */
@@ -1405,6 +1407,134 @@ int drb_ingest_buffer_free(drb_engine *e, uint8_t *buf);
  * Needs no engine and no device. */
 int drb_payload_decode(uint32_t type, const uint8_t *cmd, size_t len,
                        uint8_t *out, size_t cap, size_t *out_len);
+
+/* ---- restart: reading tan logs back ------------------------------------
+ *
+ * The records of one tan log file (internal/tan/record.go:163-311, the
+ * record reader; raftpb/update.go:183-229, Update.Unmarshal) on the host,
+ * by the code the device recovery runs (drb_tanread.hpp): per record where
+ * it starts and ends, whose it is, its State and the index range of its
+ * EntriesToSave -- what db.updateIndex (internal/tan/db.go:139-173) needs
+ * to rebuild the tan index of a log on the Go side (rebuildLogAndIndex,
+ * open.go:200-268).  Needs no engine and no device.
+ *
+ * `offset` is reader.offset() before the record (the end of the record
+ * before it: zero padding in front of a record belongs to it), `end` the
+ * offset after it.  out[0, min(*n, cap)) is filled, *n is the full count.
+ * *outcome says how the file ended; *valid_end is the offset after the last
+ * good record: where a log whose tail is an invalid record (IsInvalidRecord,
+ * record.go:153-157: DRB_TAN_ZEROED, _INVALID, _UNEXPECTED_EOF) is cut.
+ * DRB_TAN_MALFORMED: a record whose chunks check out but whose Update does
+ * not parse (MustUnmarshal panics there).  DRB_OK whatever the outcome;
+ * DRB_EINVAL for a null argument. */
+enum drb_tan_outcome {
+  DRB_TAN_EOF = 0,            /* io.EOF: the whole file read clean */
+  DRB_TAN_ZEROED = 1,         /* ErrZeroedChunk */
+  DRB_TAN_INVALID = 2,        /* ErrInvalidChunk */
+  DRB_TAN_CRC = 3,            /* ErrCRCMismatch */
+  DRB_TAN_UNEXPECTED_EOF = 4, /* io.ErrUnexpectedEOF */
+  DRB_TAN_MALFORMED = 5
+};
+typedef struct drb_tan_scan_rec {
+  uint64_t offset, end;            /* record start, offset after it */
+  uint64_t shard_id, replica_id;
+  uint64_t term, vote, commit;     /* State; has_state 0: all 0 */
+  uint64_t first_index, last_index;/* EntriesToSave; 0,0 when none */
+  uint32_t has_state, n_entries;
+} drb_tan_scan_rec;
+int drb_tan_scan(const uint8_t *log, size_t len, drb_tan_scan_rec *out,
+                 size_t cap, size_t *n, int *outcome, uint64_t *valid_end);
+
+/* drb_recover_tan: the replicas of groups [first_group, first_group +
+ * n_groups) take their raft state, log window and state machine from their
+ * tan logs, on the device -- node.replayLog (node.go:666-692), newRaft
+ * (internal/raft/raft.go:241-297), Peer Launch (peer.go:64) and the step
+ * loop's apply of (snapshot index, committed].
+ *
+ * Needs drb_engine_round(e) == 0 and the regular tan format (an engine with
+ * tan_multiplexed, or with replicas placed over ranks: DRB_EINVAL).  Calls
+ * may be repeated over disjoint group ranges; a range that holds a group an
+ * earlier call took is DRB_EINVAL and nothing is done (its log would be
+ * applied into the KV a second time).  `files` lists, per replica in
+ * log order (increasing log numbers), where each of its log files lies in
+ * `bytes`; a file table that breaks that, or points outside `bytes`, is
+ * DRB_EINVAL / DRB_ERANGE and nothing is done.
+ *
+ * base_index / base_term name the entry the logs continue from (a snapshot
+ * index; R + 1 at its term for logs of an engine started by
+ * drb_init_steady).  Entries at or below it are skipped.  The KV is not
+ * cleared: what drb_kv_import put there is the snapshot.
+ *
+ * Pass 1 validates every replica (checksums, structure, every Update and
+ * entry header) and writes nothing; pass 2 places the kept records' entries
+ * in the window and applies the committed ones.  st[(g - first_group) * R +
+ * slot] reports each replica:
+ *   DRB_REC_OK           recovered
+ *   DRB_REC_TAIL_CUT     recovered; the last log ends in an invalid record
+ *                        and is to be truncated to `offset` (rebuildLog)
+ *   DRB_REC_EMPTY        no file, or no State in any record (ErrNoSavedLog):
+ *                        the replica is left as it was
+ *   DRB_REC_CORRUPT      a CRC mismatch, an invalid record outside the last
+ *                        log, a malformed Update, a commit beyond the log, a
+ *                        rewrite of an entry at or below a persisted commit
+ *   DRB_REC_MISMATCH     a record of another ShardID / ReplicaID
+ *   DRB_REC_GAP          entries not contiguous from base_index + 1
+ *   DRB_REC_ENTRY_TYPE   an entry above the base the device apply refuses
+ *                        (config change, session-managed series, Snappy
+ *                        without entry_compression)
+ *   DRB_REC_CAPACITY     a Cmd above cmd_cap, or entries still to be
+ *                        applied that have left the window: the log reached
+ *                        W or more indexes beyond them before their commit
+ *                        was persisted, a tail that an overwrite cut off
+ *                        again included
+ *   DRB_REC_SNAPSHOT     a record that carries a Snapshot
+ *   DRB_REC_APPLY_STOPPED  the KV or its value pool filled, or a payload
+ *                        the KV does not take, while applying: the one
+ *                        status reached after the KV was touched -- the host
+ *                        imports that replica's KV again
+ * A replica with any status from DRB_REC_CORRUPT on is marked
+ * DRB_F_FALLBACK with DRB_FB_RECOVERY and otherwise unchanged (its restart
+ * goes the CPU way: drb_import_replicas, drb_import_log, drb_kv_import).
+ * With save_tan the tan writer of a recovered replica continues at
+ * {log, offset}; its stored State is non-empty when the last kept record
+ * has one -- what the db that wrote the records held (db.go:108-116). */
+enum drb_recover_code {
+  DRB_REC_OK = 0,
+  DRB_REC_TAIL_CUT = 1,
+  DRB_REC_EMPTY = 2,
+  DRB_REC_CORRUPT = 3,
+  DRB_REC_MISMATCH = 4,
+  DRB_REC_GAP = 5,
+  DRB_REC_ENTRY_TYPE = 6,
+  DRB_REC_CAPACITY = 7,
+  DRB_REC_APPLY_STOPPED = 8,
+  DRB_REC_SNAPSHOT = 9
+};
+typedef struct drb_tan_file {   /* one log file of one replica */
+  uint64_t group;
+  uint32_t slot;
+  uint32_t log;                 /* log number */
+  uint64_t off, len;            /* where its bytes lie in `bytes` */
+} drb_tan_file;
+typedef struct drb_recover_in {
+  uint64_t first_group, n_groups;  /* the groups this call recovers */
+  const uint8_t *bytes;            /* host memory, pinned or not */
+  size_t n_bytes;
+  const drb_tan_file *files;       /* per replica in log order */
+  size_t n_files;
+  uint64_t base_index, base_term;  /* the log starts after this entry */
+  uint64_t seed;                   /* raft.rand, as drb_init_steady's */
+} drb_recover_in;
+typedef struct drb_recover_status {
+  uint32_t status;   /* drb_recover_code */
+  uint32_t log;      /* the tan writer's log number */
+  uint64_t offset;   /* the tan writer's offset: after the last kept record */
+  uint64_t records, entries;  /* kept records, their entries above the base */
+  uint64_t term, vote, commit, last_index;
+  uint64_t applied;  /* index of the last entry applied */
+} drb_recover_status;
+int drb_recover_tan(drb_engine *e, const drb_recover_in *in,
+                    drb_recover_status *st);
 
 #ifdef __cplusplus
 }
