@@ -2048,7 +2048,7 @@ static uint32_t slot_list(uint32_t mask, uint32_t *n) {
 // ---------------------------------------------------------------- active list
 // A listed round (drb_round_in.listed) first lists, per (role, slot), the
 // lanes whose replica has work this round -- everything the step kernel's
-// idle rule (drb_step.hpp idle_round) would not skip -- in group order:
+// idle rule (drb_step.hpp idle_round_of) would not skip -- in group order:
 // k_active_scan ballots the rule per wave, k_active_prefix turns the
 // per-block counts into offsets, k_active_scatter writes the lanes.  The
 // step kernels then take 256 listed lanes per block, so a round where most

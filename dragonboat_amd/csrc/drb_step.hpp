@@ -2194,12 +2194,34 @@ DRB_DEV void serve_reads_lane(const View &v, uint32_t slot, uint64_t g,
 }
 
 // ------------------------------------------------------------ load/store
-template <int R, bool LEAD>
-DRB_DEV void load_rep(const Lane &L, Rep<R> &r) {
+// The round's prologue: every load whose address follows from (slot, g)
+// and the round parameters alone, issued back to back ahead of the first
+// wait (pre_load) -- one trip to memory where the state load, the idle
+// test and the pre-pass took one each.  What depends on a loaded value
+// (the record chunks behind the headers' counts, readIndex queue rows
+// >= 1, escaped index fields) follows in the second trip.
+template <int R>
+struct Pre {
+  uint32_t flags, role, fb, ri_count;
+  uint4 pk[4];
+  uint4 meta[R];       // the senders' inbox headers (own slot: unused)
+  uint64_t maxapp[R];  // ... and mbox_maxapp (non-leaders)
+  uint64_t tags;       // the inbox tag word (unlisted rounds' idle test)
+  uint4 ri_in;         // staged ReadIndex / proposal count, where this
+  uint32_t pcount;     // replica takes them (else 0)
+  uint64_t rem_m[R], rem_n[R];  // leader: the remotes
+  uint32_t rem_st[R], rem_a[R];
+  uint4 rq_c, rq_i;  // leader: readIndex queue row 0
+  uint32_t rq_cf;
+};
+
+// (EXT: the kernels that keep the lazy prologue load here, pre is unused)
+template <int R, bool LEAD, bool EXT>
+DRB_DEV void load_rep(const Lane &L, Rep<R> &r, const Pre<R> &pre) {
   const View &v = *L.v;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    const uint4 q = v.pk[pk_ix(v, c, L.slot, L.g)];
+    const uint4 q = EXT ? v.pk[pk_ix(v, c, L.slot, L.g)] : pre.pk[c];
     r.pw[4 * c] = q.x;
     r.pw[4 * c + 1] = q.y;
     r.pw[4 * c + 2] = q.z;
@@ -2224,29 +2246,33 @@ DRB_DEV void load_rep(const Lane &L, Rep<R> &r) {
   r.kv_added = 0;
   r.applied_any = false;
   r.lid_dirty = false;
-  r.flags = v.u32[u32_ix(v, W_FLAGS, L.slot, L.g)];
-  r.fb = v.u32[u32_ix(v, W_FB_REASON, L.slot, L.g)];
-  r.ri_count = v.u32[u32_ix(v, W_RI_COUNT, L.slot, L.g)];
+  r.flags = EXT ? v.u32[u32_ix(v, W_FLAGS, L.slot, L.g)] : pre.flags;
+  r.fb = EXT ? v.u32[u32_ix(v, W_FB_REASON, L.slot, L.g)] : pre.fb;
+  r.ri_count = EXT ? v.u32[u32_ix(v, W_RI_COUNT, L.slot, L.g)] : pre.ri_count;
   if (LEAD) {
 #pragma unroll
     for (int s = 0; s < R; ++s)
       rem_put<R>(L, s,
-                 RemoteV{v.rem_match[rem_ix(v, L.slot, s, L.g)],
-                         v.rem_next[rem_ix(v, L.slot, s, L.g)],
-                         v.rem_state[rem_ix(v, L.slot, s, L.g)],
-                         v.rem_active[rem_ix(v, L.slot, s, L.g)]});
+                 EXT ? RemoteV{v.rem_match[rem_ix(v, L.slot, s, L.g)],
+                               v.rem_next[rem_ix(v, L.slot, s, L.g)],
+                               v.rem_state[rem_ix(v, L.slot, s, L.g)],
+                               v.rem_active[rem_ix(v, L.slot, s, L.g)]}
+                     : RemoteV{pre.rem_m[s], pre.rem_n[s], pre.rem_st[s],
+                               pre.rem_a[s]});
     if (L.dirty) rl_of<R>(L).dirty[L.tid] = 0;
   }
 #pragma unroll
   for (int d = 0; d < DRB_RI_DEPTH; ++d) {
     if (LEAD && (uint32_t)d < r.ri_count) {
-      uint4 c = v.ri_ctx[ri_ix(v, L.slot, d, L.g)];
-      uint4 i = v.ri_idx[ri_ix(v, L.slot, d, L.g)];
+      // (the C3 kernels' row 0 came with the prologue's loads)
+      const bool ld = d || EXT;
+      const uint4 c = ld ? v.ri_ctx[ri_ix(v, L.slot, d, L.g)] : pre.rq_c;
+      const uint4 i = ld ? v.ri_idx[ri_ix(v, L.slot, d, L.g)] : pre.rq_i;
       rq_lo(L, d) = lo64(c);
       rq_hi(L, d) = hi64(c);
       r.ri_ix[d] = lo64(i);
       r.ri_fr[d] = (uint32_t)hi64(i);
-      r.ri_cf[d] = v.ri_conf[ri_ix(v, L.slot, d, L.g)];
+      r.ri_cf[d] = ld ? v.ri_conf[ri_ix(v, L.slot, d, L.g)] : pre.rq_cf;
     } else {
       if (LEAD) rq_lo(L, d) = rq_hi(L, d) = 0;
       r.ri_ix[d] = 0;
@@ -2395,10 +2421,11 @@ DRB_DEV bool prop_here(const View &v, const RoundParams &p, uint32_t slot,
 // without input: a quiesced tick only advances its tick counters
 // (node.tick node.go:1562-1579, raft.quiescedTick raft.go:650-656),
 // which the next round it runs applies at once (F_QS_BASE).
-// idle_round_of is the same rule over preloaded inputs -- the flags, the
+// idle_round_of is the rule over preloaded inputs -- the flags, the
 // slot's inbox tag word, the group's staged proposal count and ReadIndex
 // row (looked at only where prop_here / ri_here) -- which k_active_scan
-// loads all at once; idle_round loads them as the rule needs them.
+// and the C3 step kernels' prologue (pre_load) load all at once;
+// idle_round (the EXT kernels) loads them as the rule needs them.
 template <int R>
 DRB_DEV bool idle_round_of(const View &v, const RoundParams &p, uint32_t slot,
                            bool lead, uint32_t flags, uint64_t tags,
@@ -2434,6 +2461,56 @@ DRB_DEV bool idle_round(const View &v, const RoundParams &p, uint32_t slot,
        v.ri_in[(uint64_t)p.ri_slot * v.G + g].y))
     return false;
   return true;
+}
+
+// The prologue's loads (Pre, above).
+// g is the lane's group, or a valid one (0) for a lane past the launch's
+// last group: every address is in bounds, and such a lane uses no result.
+template <int R, bool LEAD>
+DRB_DEV void pre_load(const Lane &L, const RoundParams &p, uint64_t g,
+                      Pre<R> &q) {
+  const View &v = *L.v;
+  const uint32_t slot = L.slot;
+  q.flags = v.u32[u32_ix(v, W_FLAGS, slot, g)];
+  q.role = v.u32[u32_ix(v, W_ROLE, slot, g)];
+  q.fb = v.u32[u32_ix(v, W_FB_REASON, slot, g)];
+  q.ri_count = v.u32[u32_ix(v, W_RI_COUNT, slot, g)];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) q.pk[c] = v.pk[pk_ix(v, c, slot, g)];
+#pragma unroll
+  for (int s = 0; s < R; ++s) {
+    q.meta[s] = make_uint4(0, 0, 0, 0);
+    q.maxapp[s] = 0;
+    if ((uint32_t)s == slot) continue;
+    const bool rm = pair_remote(v, s, slot);
+    q.meta[s] =
+        (rm ? in_meta(L, s, slot) : v.mbox_meta)[mmeta_ix(v, L.rbuf, s, slot, g)];
+    if (!LEAD)
+      q.maxapp[s] = (rm ? in_maxapp(L, s, slot)
+                        : v.mbox_maxapp)[mmeta_ix(v, L.rbuf, s, slot, g)];
+  }
+  q.tags = 0;
+  if (!p.listed && !v.remote_mask)
+    q.tags = v.inbox_tag[((uint64_t)L.rbuf * v.R + slot) * v.G + g];
+  q.ri_in = make_uint4(0, 0, 0, 0);
+  q.pcount = 0;
+  if (ri_here(v, p, slot, LEAD))
+    q.ri_in = v.ri_in[(uint64_t)p.ri_slot * v.G + g];
+  if (prop_here(v, p, slot, LEAD))
+    q.pcount = v.prop_count[(uint64_t)p.prop_slot * v.G + g];
+  if (LEAD) {
+#pragma unroll
+    for (int s = 0; s < R; ++s) {
+      q.rem_m[s] = v.rem_match[rem_ix(v, slot, s, g)];
+      q.rem_n[s] = v.rem_next[rem_ix(v, slot, s, g)];
+      q.rem_st[s] = v.rem_state[rem_ix(v, slot, s, g)];
+      q.rem_a[s] = v.rem_active[rem_ix(v, slot, s, g)];
+    }
+    // the queue's first row: the steady state holds one request
+    q.rq_c = v.ri_ctx[ri_ix(v, slot, 0, g)];
+    q.rq_i = v.ri_idx[ri_ix(v, slot, 0, g)];
+    q.rq_cf = v.ri_conf[ri_ix(v, slot, 0, g)];
+  }
 }
 
 // The logical (x = group block, y = slot row) of this workgroup: the launch
@@ -2663,8 +2740,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLOW ? DRB_
   uint32_t qz_out = 0;      // destinations sent a Quiesce message
   uint64_t last_final = 0;  // leader: last index at the end of the round
   bool active = g < v.G;
-  uint32_t flags = active ? v.u32[u32_ix(v, W_FLAGS, slot, g)] : 0;
-  uint32_t role = active ? v.u32[u32_ix(v, W_ROLE, slot, g)] : 0;
+  // the prologue's loads, all in flight before the first use; a lane past
+  // the last group loads group 0's and uses none of it
+  // (The EXT kernels -- C5, the raft launch, forwarded proposals -- keep
+  // the lazy prologue: most of their lanes have no round or a light one,
+  // and with the batch C5 ran 1.25 % slower, profiles/prologue.)
+  Pre<R> pre;
+  uint32_t flags, role;
+  if constexpr (EXT) {
+    flags = active ? v.u32[u32_ix(v, W_FLAGS, slot, g)] : 0;
+    role = active ? v.u32[u32_ix(v, W_ROLE, slot, g)] : 0;
+  } else {
+    pre_load<R, LEAD>(L, p, active ? g : 0, pre);
+    flags = active ? pre.flags : 0;
+    role = active ? pre.role : 0;
+  }
   if (SLOW) {
     if (!(flags & DRB_F_HOSTED) || !(flags & F_SLOW)) active = false;
   } else if (!(flags & DRB_F_HOSTED) || ((role == DRB_LEADER) != LEAD)) {
@@ -2682,14 +2772,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLOW ? DRB_
     if (p.encode_saves) v.save_len[ix(v, slot, g)] = 0;
     active = false;
   }
-  if (!SLOW && active && !p.listed &&
-      idle_round<R>(v, p, slot, g, LEAD, flags))
-    active = false;
+  if (!SLOW && active && !p.listed) {
+    bool idle;
+    if constexpr (EXT)
+      idle = idle_round<R>(v, p, slot, g, LEAD, flags);
+    else
+      idle = idle_round_of<R>(v, p, slot, LEAD, flags, pre.tags, pre.pcount,
+                              pre.ri_in);
+    if (idle) active = false;
+  }
   if (active) {
     c_stepped = 1;
     if (NPH > 1) ph_t = (uint32_t)__builtin_readcyclecounter();
     Rep<R> r;
-    load_rep<R, LEAD>(L, r);
+    load_rep<R, LEAD, EXT>(L, r, pre);
     r.role = SLOW ? role : LEAD ? DRB_LEADER : DRB_FOLLOWER;
     r.votes = SLOW ? v.u32[u32_ix(v, W_VOTES, slot, g)] : 0u;
     if (SLOW) {  // off the slow list
@@ -2727,7 +2823,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLOW ? DRB_
       r.qs_exit = over_ld(L, F_QS_EXIT);
       r.qs_dirty = 0;
       // the quiesced ticks this replica skipped: only a replica that ended
-      // its last round quiesced and at rest skips rounds (idle_round), and
+      // its last round quiesced and at rest skips rounds (idle_round_of), and
       // only such a round stores the base (below)
       if (DRB_QS_EAGER ||
           (flags0 & (F_QUIESCED | F_AT_REST)) == (F_QUIESCED | F_AT_REST))
@@ -2754,6 +2850,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLOW ? DRB_
     uint32_t n_lt = 0;       // raft launch: LeaderTransfer records
     // the inbox, from the per-sender headers alone (drb_msg.hpp)
     uint64_t nin_packed = 0;  // 5-bit inbox record count per sender
+    uint64_t nrep_packed = 0;  // ... and the Replicates among them
     uint32_t total_in = 0, n_ri_msgs = 0, n_rr = 0, resp_from = 0;
     uint32_t rej_from = 0;  // senders with a rejecting ReplicateResp
     uint32_t qz_from = 0;   // senders whose Quiesce message arrived
@@ -2770,12 +2867,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLOW ? DRB_
     for (int s = 0; s < R; ++s) {
       if ((uint32_t)s == slot) continue;
       const bool rm = pair_remote(v, s, slot);
-      const uint4 meta = (rm ? in_meta(L, s, slot) : v.mbox_meta)[mmeta_ix(v, L.rbuf, s,
-                                                                 slot, g)];
+      const uint4 meta =
+          EXT ? (rm ? in_meta(L, s, slot)
+                    : v.mbox_meta)[mmeta_ix(v, L.rbuf, s, slot, g)]
+              : pre.meta[s];
       const bool cur = tag_is(meta.x, tag_prev);
       const uint32_t info = cur ? meta.y : 0u;
       const uint32_t ns = mi_count(info);
       nin_packed |= (uint64_t)ns << (5 * s);
+      nrep_packed |= (uint64_t)mi_nrep(info) << (5 * s);
       if (cur && (meta.x & MQ_QUIESCE)) qz_from |= 1u << s;
       if (SLOW) {
         // the types the raft launch handles (el_dispatch); anything else
@@ -2871,8 +2971,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLOW ? DRB_
       }
       if (info & MI_REJECT) rej_from |= 1u << s;
       if (!is_leader && mi_nrep(info))
-        max_app = umax64(max_app, (rm ? in_maxapp(L, s, slot) : v.mbox_maxapp)[mmeta_ix(
-                                      v, L.rbuf, s, slot, g)]);
+        max_app = umax64(
+            max_app,
+            EXT ? (rm ? in_maxapp(L, s, slot)
+                      : v.mbox_maxapp)[mmeta_ix(v, L.rbuf, s, slot, g)]
+                : pre.maxapp[s]);
       if (FPF && ns && (pf_s[0] < 0 || (PFS > 1 && pf_s[1] < 0))) {
         // the records go to LDS in one batch; the dispatch loop reads them
         // there (after the wait below)
@@ -2904,13 +3007,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLOW ? DRB_
         umin64(umin64(r.processed + 1, r.committed), r.sm_index);
     // staged inputs are per lane: with replicas spread over ranks a lane
     // holds R different groups, and they go to the stage slot's leader
+    // (the EXT kernels load them here)
     if (ri_here(v, p, slot, is_leader)) {
-      uint4 c = v.ri_in[(uint64_t)p.ri_slot * v.G + g];
+      const uint4 c = EXT ? v.ri_in[(uint64_t)p.ri_slot * v.G + g] : pre.ri_in;
       in_lo = lo64(c);
       in_hi = hi64(c);
     }
     if ((FWD || is_leader) && prop_here(v, p, slot, is_leader))
-      nprops = v.prop_count[(uint64_t)p.prop_slot * v.G + g];
+      nprops = EXT ? v.prop_count[(uint64_t)p.prop_slot * v.G + g]
+                   : pre.pcount;
     if (is_leader) {
       // with elections a group can hold two leaders (a stale one and the
       // new one): its entry queue goes to the hosted leader in the highest
@@ -3181,11 +3286,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLOW ? DRB_
           if (!((nin_packed >> (5 * s)) & 31u)) continue;
           const bool rm = pair_remote(v, s, slot);
           const uint4 *mb = rm ? in_mbox(L, s, slot) : v.mbox;
-          const uint4 meta = (rm ? in_meta(L, s, slot) : v.mbox_meta)[mmeta_ix(
-              v, L.rbuf, s, slot, g)];
-          const uint64_t sterm = hi64(meta);
+          // the sender's term and counts.  Outside the raft launch the
+          // pre-pass has fallen back unless every record that carries the
+          // header term (MI_TERM) carries this replica's, which no fast
+          // round changes, and the counts are the pre-pass's: no second
+          // load of the header, which would wait behind the round's stores.
+          // The raft launch's sender terms differ, and the EXT kernels keep
+          // their prologue and loop as they were: they load the header.
+          uint64_t sterm = term0;
+          uint32_t nrp_s = (uint32_t)(nrep_packed >> (5 * s)) & 31u;
+          uint32_t noth_s = ((uint32_t)(nin_packed >> (5 * s)) & 31u) - nrp_s;
+          if (EXT) {
+            const uint4 meta = (rm ? in_meta(L, s, slot)
+                                   : v.mbox_meta)[mmeta_ix(v, L.rbuf, s, slot, g)];
+            sterm = hi64(meta);
+            nrp_s = mi_nrep(meta.y);
+            noth_s = mi_noth(meta.y);
+          }
           // records of this pass: the Replicates, then the others
-          const uint32_t cnt = pass == 0 ? mi_nrep(meta.y) : mi_noth(meta.y);
+          const uint32_t cnt = pass == 0 ? nrp_s : noth_s;
           EntSrc src;
           src.remote = rm;
           src.lo = 0;
