@@ -80,11 +80,14 @@ constexpr int NUM_U64_EXPORTED = F_RING_LO;
 //   w11 term - appliedToTerm | (term - prevTerm) << 16,
 //   w12 term - smTerm | electionTick << 16,
 //   w13 heartbeatTick | randomizedElectionTimeout << 16,
-//   w14 vote | leaderID << 8 | prevVote << 16, w15 0.
+//   w14 vote | leaderID << 8 | prevVote << 16,
+//   w15 tick_count delta | kv_count delta << 16.
 // A value that does not fit stores the field's escape code and lives in
-// the u64 field array, which also keeps tick_count and kv_count.  A round
-// reads and writes 64 B of state per replica instead of ~340 B of u64
-// fields.
+// the u64 field array.  tick_count and kv_count are their u64 field plus
+// the record's 16-bit delta: a round counts in the record it stores anyway,
+// and folds a delta into its field only when it would pass 0xffff
+// (pk_count_add).  A round reads and writes 64 B of state per replica
+// instead of ~340 B of u64 fields.
 enum PIdx : int {
   PI_COMMITTED = 0,
   PI_PROCESSED,
@@ -155,9 +158,26 @@ __host__ __device__ inline uint32_t pk_id_code(uint64_t x) {
   return x < PK_ESC8 ? (uint32_t)x : PK_ESC8;
 }
 
+// the counter deltas of word 15: half 0 tick_count, half 1 kv_count
+constexpr int PK_CNT_WORD = 15, PK_CNT_TICK = 0, PK_CNT_KV = 1;
+// Adds n (< 2^31) to the delta in half `hi` of word 15.  Returns 0 when the
+// delta holds the sum; else the amount the caller adds to the u64 field
+// (the whole delta and n), the delta being zero afterwards.
+__host__ __device__ inline uint32_t pk_count_add(uint32_t *w, int hi,
+                                                 uint32_t n) {
+  const uint32_t d = pk_half(w, PK_CNT_WORD, hi) + n;
+  if (d <= 0xffffu) {
+    pk_set_half(w, PK_CNT_WORD, hi, d);
+    return 0;
+  }
+  pk_set_half(w, PK_CNT_WORD, hi, 0);
+  return d;
+}
+
 // the whole record from / to field values indexed by U64Field (vals),
-// escapes through the overflow array `over` (same index); tick_count and
-// kv_count are not in the record
+// escapes through the overflow array `over` (same index).  pk_encode writes
+// tick_count and kv_count whole to their fields (the caller stores vals[]
+// there) and leaves the deltas zero; pk_decode returns field + delta
 __host__ __device__ inline void pk_encode(uint32_t *w, const uint64_t *vals,
                                           uint64_t *over) {
   const uint64_t last = vals[F_LAST_INDEX], term = vals[F_TERM];
@@ -223,8 +243,9 @@ __host__ __device__ inline void pk_decode(const uint32_t *w,
     const uint32_t c = (w[14] >> (8 * k)) & 0xffu;
     vals[df[k]] = c == PK_ESC8 ? over[df[k]] : c;
   }
-  vals[F_TICK_COUNT] = over[F_TICK_COUNT];
-  vals[F_KV_COUNT] = over[F_KV_COUNT];
+  vals[F_TICK_COUNT] =
+      over[F_TICK_COUNT] + pk_half(w, PK_CNT_WORD, PK_CNT_TICK);
+  vals[F_KV_COUNT] = over[F_KV_COUNT] + pk_half(w, PK_CNT_WORD, PK_CNT_KV);
   for (int f = F_QS_TICK; f <= F_QS_EXIT; ++f) vals[f] = over[f];
   vals[F_RNG] = over[F_RNG];
   vals[F_QS_BASE] = over[F_QS_BASE];

@@ -103,14 +103,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
   // Every load of the lane first, none depending on another: the flags,
   // the record, the inbox headers and -- speculatively, before the headers
   // say how many there are -- the first non-Replicate record of each
-  // sender, the quiesce state and tick counter, the leader's remotes.  A
+  // sender, the quiesce state, the leader's remotes (the tick counter is
+  // in the record).  A
   // lane then waits for one memory round trip, where the full kernel's
   // chain of decisions waits for several.
   const bool valid = g < v.G;
   const bool qon = v.quiesce;
   uint32_t flags = 0, role = 0, fbw = 0, ric = 0, pcount = 0;
   uint4 pkq[4], meta[R], rec[R][NREC], riq = make_uint4(0, 0, 0, 0);
-  uint64_t qsv[5] = {0, 0, 0, 0, 0}, tick_count = 0;
+  uint64_t qsv[5] = {0, 0, 0, 0, 0};
   uint64_t rmatch[R];
   uint32_t rstate[R], ractive[R];
   // (meta, rec, rmatch and rstate of the lane's own slot are never loaded
@@ -145,7 +146,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
       qsv[3] = v.u64[u64_ix(v, F_QS_EXIT, slot, g)];
       qsv[4] = v.u64[u64_ix(v, F_QS_BASE, slot, g)];
     }
-    if (p.tick) tick_count = v.u64[u64_ix(v, F_TICK_COUNT, slot, g)];
     if (LEAD) {
 #pragma unroll
       for (int s = 0; s < R; ++s) {
@@ -404,7 +404,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
       if (p.tick && quiet) {
         r.election_tick++;  // raft.quiescedTick (raft.go:650-656)
       } else if (p.tick) {
-        over_st(L, F_TICK_COUNT, tick_count + 1);
+        // (tick_count: in the record's chunk 3, stored for the tick anyway)
+        count_add(L, r, PK_CNT_TICK, F_TICK_COUNT, 1);
         if (LEAD) {
           r.election_tick++;
           if (r.election_tick >= v.election_rtt) {

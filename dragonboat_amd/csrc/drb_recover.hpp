@@ -231,8 +231,15 @@ __global__ __launch_bounds__(REC_BLOCK) void k_recover_place(View v,
   const bool ok =
       tr_replay(files, pl, rec_limits(v, p, slot, g), pc, &applied);
   st.applied = applied;
-  // KVTest.Count: the updates applied
-  v.u64[u64_ix(v, F_KV_COUNT, slot, g)] += pc.r.kv_added;
+  // KVTest.Count: the updates applied, and what the replica's record had
+  // counted since the field was last written (word 15's delta, which the
+  // record loses below or keeps zeroed here)
+  {
+    uint4 c3 = v.pk[pk_ix(v, 3, slot, g)];
+    v.u64[u64_ix(v, F_KV_COUNT, slot, g)] += pc.r.kv_added + (c3.w >> 16);
+    c3.w &= 0xffffu;
+    v.pk[pk_ix(v, 3, slot, g)] = c3;
+  }
   if (!ok) {  // the KV filled (or refused a payload) part way
     st.status = TRS_APPLY_STOPPED;
     v.u32[u32_ix(v, W_FLAGS, slot, g)] |= DRB_F_FALLBACK;

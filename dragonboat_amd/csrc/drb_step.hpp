@@ -127,8 +127,9 @@ enum : int {
 // fields most of the round uses are decoded into registers; the rest
 // (vote, the randomized timeout, Peer's prevState, node's confirmed/pushed
 // indexes, appliedTo*, sm_term) stay encoded in the record words and are
-// read / written through ld_f / st_f.  tick_count and kv_count are plain
-// u64 counters, read-modify-written where the round changes them.
+// read / written through ld_f / st_f.  tick_count and kv_count are counted
+// in the record's word 15 (count_add); their u64 fields are touched only
+// when a 16-bit delta is folded in.
 template <int R>
 struct Rep {
   uint32_t pw[16];  // the packed record (index offsets relative to base0)
@@ -321,6 +322,15 @@ DRB_DEV uint64_t over_ld(const Lane &L, int f) {
 DRB_DEV void over_st(const Lane &L, int f, uint64_t x) {
   L.v->u64[u64_ix(*L.v, f, L.slot, L.g)] = x;
 }
+// tick_count (hi = PK_CNT_TICK, field F_TICK_COUNT) or kv_count += n in
+// the record; the u64 field only when the delta would pass 0xffff.  A round
+// that does not store its record (a fallback of the pre-pass) has not
+// counted yet, so its deltas stay the pre-round ones.
+template <int R>
+DRB_DEV void count_add(const Lane &L, Rep<R> &r, int hi, int f, uint32_t n) {
+  const uint32_t fold = pk_count_add(r.pw, hi, n);
+  if (fold) over_st(L, f, over_ld(L, f) + fold);
+}
 // index field i (a PIdx constant): offset from `base` in the record
 template <int R>
 DRB_DEV uint64_t pi_get(const Lane &L, const Rep<R> &r, int i) {
@@ -387,7 +397,7 @@ DRB_DEV uint64_t ld_f(const Lane &L, const Rep<R> &r, int f) {
     case F_CONFIRMED_INDEX: return pi_get(L, r, PI_CONFIRMED);
     case F_PUSHED_INDEX: return pi_get(L, r, PI_PUSHED);
     case F_PREV_COMMIT: return pi_get(L, r, PI_PREV_COMMIT);
-    default: return over_ld(L, f);  // tick_count, kv_count
+    default: return over_ld(L, f);  // a field the record does not hold
   }
 }
 template <int R>
@@ -404,7 +414,7 @@ DRB_DEV void st_f(const Lane &L, Rep<R> &r, int f, uint64_t x) {
     case F_CONFIRMED_INDEX: pi_put(L, r, PI_CONFIRMED, x, r.base0); break;
     case F_PUSHED_INDEX: pi_put(L, r, PI_PUSHED, x, r.base0); break;
     case F_PREV_COMMIT: pi_put(L, r, PI_PREV_COMMIT, x, r.base0); break;
-    default: over_st(L, f, x); break;  // tick_count, kv_count
+    default: over_st(L, f, x); break;  // a field the record does not hold
   }
 }
 
@@ -1561,7 +1571,7 @@ DRB_DEV void el_dispatch(const Lane &L, Rep<R> &r, int s, const Msg &m,
 template <int R>
 DRB_DEV void el_tick(const Lane &L, Rep<R> &r, bool xfer = false) {
   const View &v = *L.v;
-  over_st(L, F_TICK_COUNT, over_ld(L, F_TICK_COUNT) + 1);
+  count_add(L, r, PK_CNT_TICK, F_TICK_COUNT, 1);
   if (r.role == DRB_LEADER) {
     r.election_tick++;
     const bool abort_xfer =
@@ -1792,10 +1802,26 @@ static __device__ __noinline__ uint32_t snappy_to_row(const uint4 *cmd,
 template <int R, bool EXT>
 DRB_DEV int apply_entry(const Lane &L, Rep<R> &r, uint64_t index) {
   const View &v = *L.v;
-  uint4 m0 = v.ring[ring_ix(v, L.slot, index, 0, L.g)];
+  // The C3 kernels (!EXT) issue every load of the entry back to back, ahead
+  // of the early returns: the meta chunks 1 and 2 and the Cmd's first 64
+  // bytes (rows of the replica's own resident window, always in bounds)
+  // arrive in one memory round trip, the KV probe group in a second.  The
+  // entry's term is the replica's on the log's tail (log_term's invariant);
+  // meta chunk 0 holds nothing else the apply needs.  The EXT kernels load
+  // as the decisions need them.
   uint4 m1 = v.ring[ring_ix(v, L.slot, index, 1, L.g)];
   uint4 m2 = v.ring[ring_ix(v, L.slot, index, 2, L.g)];
-  uint64_t term = lo64(m0);
+  Cmd4 cmd;
+  cmd.c1 = cmd.c2 = cmd.c3 = make_uint4(0, 0, 0, 0);
+  if (!EXT) {
+    cmd.c0 = v.ring[ring_ix(v, L.slot, index, ENT_META, L.g)];
+    if (v.C16 > 1) cmd.c1 = v.ring[ring_ix(v, L.slot, index, ENT_META + 1, L.g)];
+    if (v.C16 > 2) cmd.c2 = v.ring[ring_ix(v, L.slot, index, ENT_META + 2, L.g)];
+    if (v.C16 > 3) cmd.c3 = v.ring[ring_ix(v, L.slot, index, ENT_META + 3, L.g)];
+  }
+  uint64_t term = r.term;
+  if (EXT || index < r.term_start)
+    term = lo64(v.ring[ring_ix(v, L.slot, index, 0, L.g)]);
   uint64_t client_id = lo64(m1), series_id = hi64(m1);
   uint32_t type = m2.z, clen = m2.w;
   if (type == DRB_ENTRY_CONFIG_CHANGE) return -1;
@@ -1808,12 +1834,12 @@ DRB_DEV int apply_entry(const Lane &L, Rep<R> &r, uint64_t index) {
   }
   if (series_id != 0) return -1;  // sessions stay on the CPU path
   // the Cmd's first 64 bytes in registers: the PBKV header lies there
-  Cmd4 cmd;
-  cmd.c0 = v.ring[ring_ix(v, L.slot, index, ENT_META, L.g)];
-  cmd.c1 = cmd.c2 = cmd.c3 = make_uint4(0, 0, 0, 0);
-  if (v.C16 > 1) cmd.c1 = v.ring[ring_ix(v, L.slot, index, ENT_META + 1, L.g)];
-  if (v.C16 > 2) cmd.c2 = v.ring[ring_ix(v, L.slot, index, ENT_META + 2, L.g)];
-  if (v.C16 > 3) cmd.c3 = v.ring[ring_ix(v, L.slot, index, ENT_META + 3, L.g)];
+  if (EXT) {
+    cmd.c0 = v.ring[ring_ix(v, L.slot, index, ENT_META, L.g)];
+    if (v.C16 > 1) cmd.c1 = v.ring[ring_ix(v, L.slot, index, ENT_META + 1, L.g)];
+    if (v.C16 > 2) cmd.c2 = v.ring[ring_ix(v, L.slot, index, ENT_META + 2, L.g)];
+    if (v.C16 > 3) cmd.c3 = v.ring[ring_ix(v, L.slot, index, ENT_META + 3, L.g)];
+  }
   uint32_t off = 0, plen = clen;
   // EXT: a decoded Snappy payload's chunks (the replica's row of v.snap)
   const uint4 *pay = nullptr;
@@ -2310,8 +2336,6 @@ DRB_DEV void store_rep(const Lane &L, Rep<R> &r, uint32_t flags0,
   pu_put(L, r, 12, 1, F_ELECTION_TICK, r.election_tick);
   if (LEAD) pu_put(L, r, 13, 0, F_HEARTBEAT_TICK, r.heartbeat_tick);
   if (r.applied_any) pt_put(L, r, 12, 0, F_SM_TERM, r.sm_term);
-  if (r.kv_added)
-    over_st(L, F_KV_COUNT, over_ld(L, F_KV_COUNT) + r.kv_added);
   r.pw[0] = (uint32_t)r.last;
   r.pw[1] = (uint32_t)(r.last >> 32);
 #pragma unroll
@@ -2489,8 +2513,10 @@ DRB_DEV void pre_load(const Lane &L, const RoundParams &p, uint64_t g,
       q.maxapp[s] = (rm ? in_maxapp(L, s, slot)
                         : v.mbox_maxapp)[mmeta_ix(v, L.rbuf, s, slot, g)];
   }
+  // (idle_round_of returns before the tags when the round ticks with
+  // Quiesce off -- every round of the C3 steady state; uniform)
   q.tags = 0;
-  if (!p.listed && !v.remote_mask)
+  if (!p.listed && !v.remote_mask && !(p.tick && !v.quiesce))
     q.tags = v.inbox_tag[((uint64_t)L.rbuf * v.R + slot) * v.G + g];
   q.ri_in = make_uint4(0, 0, 0, 0);
   q.pcount = 0;
@@ -3356,7 +3382,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLOW ? DRB_
       } else if (SLOW && p.tick) {
         el_tick(L, r);  // any role; may campaign or step down
       } else if (p.tick) {
-        over_st(L, F_TICK_COUNT, over_ld(L, F_TICK_COUNT) + 1);
+        count_add(L, r, PK_CNT_TICK, F_TICK_COUNT, 1);
         if (is_leader) {
           r.election_tick++;
           if (r.election_tick >= v.election_rtt) {
@@ -3531,6 +3557,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SLOW ? DRB_
             c_commit++;
         }
       }
+      // KVTest.Count, in the record (here, not in store_rep: the follower
+      // spills one register less)
+      if (r.kv_added) count_add(L, r, PK_CNT_KV, F_KV_COUNT, r.kv_added);
       DRB_PH(5);  // apply
       // the entry rows of remote followers' planes: [lowest sent, last]
       if (LEAD && v.remote_mask) {
