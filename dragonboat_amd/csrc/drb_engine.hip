@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -21,6 +22,7 @@
 #include "drb_step.hpp"
 #include "drb_launch.hpp"
 #include "drb_hsa.hpp"
+#include "drb_res.hpp"
 
 using namespace drb;
 
@@ -34,14 +36,19 @@ using namespace drb;
     }                                                                    \
   } while (0)
 
+// Every device resource has one owner (drb_res.hpp): the members below and
+// those of the lazily built WireState / IngestState / WorkerState free
+// themselves when the engine goes.  What must happen first -- the streams
+// drained, bound peers drained, the drain thread joined -- is
+// drb_engine_destroy's explicit quiesce, never the declaration order.
 struct drb_engine {
   drb_config cfg;
   View v;
   View *dview;  // device copy of v (kernels read it with scalar loads)
-  hipStream_t stream;
-  hipStream_t stream2;            // the follower kernel of a round
-  hipEvent_t ev_fork, ev_join;    // stream -> stream2 -> stream
-  hipStream_t stream_h2d;         // drb_stage_proposals uploads
+  Stream stream;
+  Stream stream2;                 // the follower kernel of a round
+  Event ev_fork, ev_join;         // stream -> stream2 -> stream
+  Stream stream_h2d;              // drb_stage_proposals uploads
   HsaXfer xfer;  // the engine's own SDMA transfers (drb_hsa.hpp)
   // sticky: a multi-round call failed after some of its rounds were
   // enqueued, so the device ran rounds the host did not account for (round
@@ -49,20 +56,20 @@ struct drb_engine {
   int failed = 0;
   // drb_set_session_clients: per lane the ClientID of the host's NoOP
   // session of its group ([G], null until set)
-  uint64_t *sess_client = nullptr;
+  DevBuf sess_client;
   // the lean kernel of listed rounds off (drb_config.no_lean: A/B only)
   bool no_lean = false;
   // drb_exchange_local_bind: the engines of the group, this one included,
   // and per rank their outbox planes (host copy; v.peers the device one)
   std::vector<drb_engine *> bound;
   std::vector<PeerPlanes> peers_host;
-  hipEvent_t ev_staged;           // upload done -> layout kernel
-  hipEvent_t ev_stage_free;       // layout kernel done -> next upload
-  hipEvent_t ev_uploaded;         // packed upload done -> host arrays free
+  Event ev_staged;                // upload done -> layout kernel
+  Event ev_stage_free;            // layout kernel done -> next upload
+  Event ev_uploaded;              // packed upload done -> host arrays free
   // drb_exchange_local: this engine's round done (its outbox planes may be
   // copied), and the copies into its inbound planes done (its senders'
   // next rounds may overwrite their outbox planes)
-  hipEvent_t ev_xsend = nullptr, ev_xrecv = nullptr;
+  Event ev_xsend, ev_xrecv;
   // the last round whose remote planes were exchanged (or enqueued, drb_
   // exchange_mark): ingest into remote planes waits for it (DRB_EAGAIN)
   uint64_t exchanged_round = 0;
@@ -70,21 +77,19 @@ struct drb_engine {
   // (drb_step_round_async, the generators, drb_stage_proposals), so that
   // drb_stage_proposals_packed lays a slot out on the copy stream while
   // rounds on other slots run
-  std::vector<hipEvent_t> ev_prop;
-  uint64_t round;
-  uint64_t ticks;  // LocalTicks delivered so far (RoundParams.tick_no)
+  std::vector<Event> ev_prop;
+  uint64_t round = 0;
+  uint64_t ticks = 0;  // LocalTicks delivered so far (RoundParams.tick_no)
   uint64_t committed_round = 0;  // drb_commit_round (durable_log)
-  uint64_t bytes;
-  std::vector<void *> allocs;
+  uint64_t bytes = 0;
+  std::vector<DevBuf> allocs;  // the fixed arrays (dalloc)
   uint64_t ctr_rows = 0;                     // workgroup counter rows
   uint32_t *xcount = nullptr;                // [R][R] plane summaries
   uint32_t role_slots[2] = {0, 0};           // role map (launch_step)
   uint32_t *role_dev = nullptr;
   unsigned long long *ctr_total = nullptr;   // their sum (read_counters)
-  void *scratch;
-  size_t scratch_bytes;
-  void *stage_buf = nullptr;  // drb_stage_proposals upload (grow-only)
-  size_t stage_bytes = 0;
+  DevBuf scratch;    // gather / scatter and the exports (grow-only)
+  DevBuf stage_buf;  // drb_stage_proposals upload (grow-only)
   struct WireState *wire = nullptr;          // drb_encode_wire (drb_wire.hpp)
   struct IngestState *ingest = nullptr;      // drb_ingest_wire (drb_ingest.hpp)
   struct WorkerState *worker = nullptr;      // drb_worker_export (drb_worker.hpp)
@@ -100,8 +105,7 @@ struct drb_engine {
   // their count per ctx and key space (drb_export_read_results)
   uint64_t reads_round = ~0ull;
   uint32_t reads_n = 0, reads_ks = 0;
-  void *xout = nullptr;  // batch exports' device output (grow-only)
-  size_t xout_bytes = 0;
+  DevBuf xout;  // batch exports' device output (grow-only)
   // drb_exchange_bytes: inbound plane bytes of the device pull (a device
   // counter) and of region copies (host-side sum)
   unsigned long long *xpull_bytes = nullptr;
@@ -127,24 +131,20 @@ template <typename T>
 static int dalloc(drb_engine *e, T **p, uint64_t count) {
   uint64_t b = count * sizeof(T);
   if (b == 0) b = 16;
-  void *q = nullptr;
-  HIPCHK(hipMalloc(&q, b));
-  HIPCHK(hipMemsetAsync(q, 0, b, e->stream));
-  e->allocs.push_back(q);
+  DevBuf q;
+  if (q.reserve(b)) return DRB_EDEVICE;
+  HIPCHK(hipMemsetAsync(q.p, 0, b, e->stream));
+  *p = q.as<T>();
+  e->allocs.push_back(std::move(q));
   e->bytes += b;
-  *p = (T *)q;
   return DRB_OK;
 }
 
 static int scratch(drb_engine *e, size_t bytes, void **out) {
-  if (bytes > e->scratch_bytes) {
-    if (e->scratch) HIPCHK(hipFree(e->scratch));
-    e->scratch = nullptr;
-    size_t b = std::max(bytes, (size_t)1 << 20);
-    HIPCHK(hipMalloc(&e->scratch, b));
-    e->scratch_bytes = b;
-  }
-  *out = e->scratch;
+  if (bytes > e->scratch.cap &&
+      e->scratch.reserve(std::max(bytes, (size_t)1 << 20)))
+    return DRB_EDEVICE;
+  *out = e->scratch.p;
   return DRB_OK;
 }
 
@@ -226,9 +226,13 @@ __global__ void k_fill_u64(uint64_t *p, uint64_t n, uint64_t val) {
 }
 
 // ---------------------------------------------------------------- create
-extern "C" int drb_engine_create(const drb_config *cfg, drb_engine **out) {
-  if (!cfg || !out) return DRB_EINVAL;
-  *out = nullptr;
+// the multiplexed tan's records per log and round (View.tanm_J)
+static uint32_t tanm_records(uint64_t G) {
+  return (uint32_t)((((G + 15) / 16) + 255) & ~255ull);
+}
+
+// Every check of a configuration, before anything touches a device.
+static int validate_config(const drb_config *cfg) {
   if (cfg->num_groups == 0 || cfg->num_replicas < 1 ||
       cfg->num_replicas > DRB_MAX_REPLICAS)
     return DRB_EINVAL;
@@ -278,50 +282,48 @@ extern "C" int drb_engine_create(const drb_config *cfg, drb_engine **out) {
   // limitSize never binds inside the window (entryutils.go:50-63)
   if ((uint64_t)cfg->window * (128 + cfg->cmd_cap) > MAX_ENTRY_SIZE)
     return DRB_EINVAL;
-  drb_engine *e = new drb_engine();
-  e->cfg = *cfg;
-  e->round = 0;
-  e->ticks = 0;
-  e->bytes = 0;
-  e->scratch = nullptr;
-  e->scratch_bytes = 0;
-  if (cfg->host_copies > 1 || cfg->entry_compression > 1) {
-    delete e;
+  if (cfg->host_copies > 1 || cfg->entry_compression > 1) return DRB_EINVAL;
+  // the ranks' groups cover total_groups (0: all of them)
+  if (cfg->total_groups >
+      cfg->num_groups * std::max<uint64_t>(cfg->place_world, 1))
     return DRB_EINVAL;
-  }
+  // (overflow buckets are linked by 32-bit number, ~0 the end of a chain)
+  if (cfg->kv_overflow_buckets >= 0xffffffffull) return DRB_ERANGE;
+  // the multiplexed tan addresses a log's staged round by 32-bit byte offset
+  if (cfg->save_tan && cfg->tan_multiplexed &&
+      (uint64_t)tanm_records(cfg->num_groups) * cfg->save_cap > 0xffffffffull)
+    return DRB_ERANGE;
+  return DRB_OK;
+}
+
+namespace {
+struct EngineDestroy {
+  void operator()(drb_engine *e) const { (void)drb_engine_destroy(e); }
+};
+}  // namespace
+
+extern "C" int drb_engine_create(const drb_config *cfg, drb_engine **out) {
+  if (!cfg || !out) return DRB_EINVAL;
+  *out = nullptr;
+  if (int rc = validate_config(cfg)) return rc;
+  // (from here every failure is a plain return: the engine goes as
+  // drb_engine_destroy takes it down)
+  std::unique_ptr<drb_engine, EngineDestroy> owner(new drb_engine());
+  drb_engine *e = owner.get();
+  e->cfg = *cfg;
   // (host_copies: HIP copies, as when the SDMA engines are unavailable)
   if (cfg->host_copies) e->xfer.state = -1;
   e->no_lean = cfg->no_lean != 0;
   if (hipSetDevice(cfg->device) != hipSuccess ||
-      hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) !=
-          hipSuccess ||
-      hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking) !=
-          hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) !=
-          hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) !=
-          hipSuccess ||
-      hipStreamCreateWithFlags(&e->stream_h2d, hipStreamNonBlocking) !=
-          hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_staged, hipEventDisableTiming) !=
-          hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_stage_free, hipEventDisableTiming) !=
-          hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_uploaded, hipEventDisableTiming) !=
-          hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_xsend, hipEventDisableTiming) !=
-          hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_xrecv, hipEventDisableTiming) !=
-          hipSuccess) {
-    delete e;
+      e->stream.create() != hipSuccess || e->stream2.create() != hipSuccess ||
+      e->stream_h2d.create() != hipSuccess)
     return DRB_EDEVICE;
-  }
   e->ev_prop.resize(cfg->prop_slots);
-  for (auto &ev : e->ev_prop)
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-      delete e;
-      return DRB_EDEVICE;
-    }
+  for (Event *ev : {&e->ev_fork, &e->ev_join, &e->ev_staged, &e->ev_stage_free,
+                    &e->ev_uploaded, &e->ev_xsend, &e->ev_xrecv})
+    if (ev->create() != hipSuccess) return DRB_EDEVICE;
+  for (Event &ev : e->ev_prop)
+    if (ev.create() != hipSuccess) return DRB_EDEVICE;
   View &v = e->v;
   memset(&v, 0, sizeof(v));
   const uint64_t G = cfg->num_groups, R = cfg->num_replicas;
@@ -359,10 +361,6 @@ extern "C" int drb_engine_create(const drb_config *cfg, drb_engine **out) {
   v.place_world = cfg->place_world > 1 ? cfg->place_world : 1;
   v.place_rank = v.place_world > 1 ? cfg->place_rank : 0;
   v.total_groups = cfg->total_groups ? cfg->total_groups : G * v.place_world;
-  if (v.total_groups > G * v.place_world) {
-    delete e;
-    return DRB_EINVAL;
-  }
   v.remote_mask = 0;
   if (v.place_world > 1)
     for (uint32_t a = 0; a < R; ++a)
@@ -396,10 +394,6 @@ extern "C" int drb_engine_create(const drb_config *cfg, drb_engine **out) {
     if (ph[0] == '1') rc |= dalloc(e, &v.phase, 16);
   v.kv_ovf_cap = cfg->kv_overflow_buckets;
   if (v.kv_ovf_cap) {
-    if (v.kv_ovf_cap >= 0xffffffffull) {
-      delete e;
-      return DRB_ERANGE;
-    }
     rc |= dalloc(e, &v.kv_ovf, v.kv_ovf_cap * 4 * v.KVW);
     rc |= dalloc(e, &v.kv_ovf_next, v.kv_ovf_cap);
     rc |= dalloc(e, &v.kv_ovf_head, R * G);
@@ -443,9 +437,8 @@ extern "C" int drb_engine_create(const drb_config *cfg, drb_engine **out) {
     // the multiplexed tan stages each log's round in save_buf: 16 logs per
     // slot of at most tanm_J records each
     v.tan_mux = cfg->save_tan && cfg->tan_multiplexed ? 1u : 0u;
-    v.tanm_J = (uint32_t)((((G + 15) / 16) + 255) & ~255ull);
+    v.tanm_J = tanm_records(G);
     v.tanm_cap16 = (uint64_t)v.tanm_J * v.save_cap16;
-    if (v.tan_mux && v.tanm_cap16 * 16 > 0xffffffffull) return DRB_ERANGE;
     rc |= dalloc(e, &v.save_buf,
                  std::max<uint64_t>(R * G, v.tan_mux ? R * 16 * v.tanm_J : 0) *
                      v.save_cap16);
@@ -523,18 +516,15 @@ extern "C" int drb_engine_create(const drb_config *cfg, drb_engine **out) {
   if (!rc && hipMemcpyAsync(e->dview, &e->v, sizeof(View),
                             hipMemcpyHostToDevice, e->stream) != hipSuccess)
     rc = 1;
-  if (rc || hipStreamSynchronize(e->stream) != hipSuccess) {
-    drb_engine_destroy(e);
-    return DRB_ENOMEM;
-  }
-  *out = e;
+  if (rc || hipStreamSynchronize(e->stream) != hipSuccess) return DRB_ENOMEM;
+  *out = owner.release();
   return DRB_OK;
 }
 
 extern "C" int drb_engine_destroy(drb_engine *e) {
   if (!e) return DRB_EINVAL;
-  (void)hipStreamSynchronize(e->stream);
-  (void)hipStreamSynchronize(e->stream2);
+  if (e->stream) (void)hipStreamSynchronize(e->stream);
+  if (e->stream2) (void)hipStreamSynchronize(e->stream2);
   // bound peers read this engine's outbox planes: their work drains first,
   // and their later rounds fail (their remote planes are gone)
   for (drb_engine *o : e->bound) {
@@ -544,26 +534,18 @@ extern "C" int drb_engine_destroy(drb_engine *e) {
     o->bound.erase(std::remove(o->bound.begin(), o->bound.end(), e),
                    o->bound.end());
   }
-  for (void *p : e->allocs) (void)hipFree(p);
-  if (e->scratch) (void)hipFree(e->scratch);
-  if (e->stage_buf) (void)hipFree(e->stage_buf);
-  if (e->xout) (void)hipFree(e->xout);
+  // the engine's own arrays first (nothing below reads them: the drain
+  // thread copies from the worker's staging only)
+  e->allocs.clear();
+  e->scratch.reset();
+  e->stage_buf.reset();
+  e->xout.reset();
+  // the drain thread and its copies stop before their staging goes; the
+  // worker's signals go before the HSA runtime they belong to
   wire_free(e);
   ingest_free(e->ingest);
   worker_free(e);
-  if (e->sess_client) (void)hipFree(e->sess_client);
   hsa_xfer_fini(&e->xfer);
-  (void)hipEventDestroy(e->ev_fork);
-  (void)hipEventDestroy(e->ev_join);
-  (void)hipEventDestroy(e->ev_staged);
-  (void)hipEventDestroy(e->ev_stage_free);
-  (void)hipEventDestroy(e->ev_uploaded);
-  if (e->ev_xsend) (void)hipEventDestroy(e->ev_xsend);
-  if (e->ev_xrecv) (void)hipEventDestroy(e->ev_xrecv);
-  for (auto &ev : e->ev_prop) (void)hipEventDestroy(ev);
-  (void)hipStreamDestroy(e->stream_h2d);
-  (void)hipStreamDestroy(e->stream2);
-  (void)hipStreamDestroy(e->stream);
   delete e;
   return DRB_OK;
 }
@@ -1145,15 +1127,12 @@ extern "C" int drb_stage_proposals(drb_engine *e, uint32_t slot,
   const size_t ent_b = (size_t)G * v.max_props * sizeof(drb_entry);
   const size_t cnt_off = ent_b, pool_off = (cnt_off + G * 4 + 255) & ~(size_t)255;
   const size_t need = pool_off + std::max<uint64_t>(pool_len, 16);
-  if (need > e->stage_bytes) {
+  if (need > e->stage_buf.cap) {
     HIPCHK(hipStreamSynchronize(e->stream));  // the buffer may be in use
     HIPCHK(hipStreamSynchronize(e->stream_h2d));
-    if (e->stage_buf) HIPCHK(hipFree(e->stage_buf));
-    e->stage_buf = nullptr;
-    HIPCHK(hipMalloc(&e->stage_buf, need));
-    e->stage_bytes = need;
+    if (e->stage_buf.reserve(need)) return DRB_EDEVICE;
   }
-  uint8_t *d = (uint8_t *)e->stage_buf;
+  uint8_t *d = e->stage_buf.as<uint8_t>();
   // The upload runs on its own stream, so it overlaps a round still
   // running on the engine stream; it starts once the previous call's layout
   // kernel has consumed the upload buffer.  The call returns when the host
@@ -1268,7 +1247,7 @@ static int stage_packed(drb_engine *e, uint32_t slot, uint32_t type,
   if (!counts || (n_entries && (!keys || !cmd_lens)) || (pool_len && !pool))
     return DRB_EINVAL;
   // without client ids: the registered session clients
-  if (n_entries && !client_ids && !e->sess_client) return DRB_EINVAL;
+  if (n_entries && !client_ids && !e->sess_client.p) return DRB_EINVAL;
   const View &v = e->v;
   const uint64_t G = v.G, n = n_entries;
   // the counts before anything reads the entry arrays (they bound n); the
@@ -1303,15 +1282,12 @@ static int stage_packed(drb_engine *e, uint32_t slot, uint32_t type,
   const size_t o_e0 = al(std::max<size_t>(up, o_pool + 16)),
                o_off = o_e0 + al(4 * G), o_tmp = o_off + al(4 * n1),
                need = o_tmp + al(std::max(tb1, tb2));
-  if (need > e->stage_bytes) {
+  if (need > e->stage_buf.cap) {
     HIPCHK(hipStreamSynchronize(e->stream));  // the buffer may be in use
     HIPCHK(hipStreamSynchronize(e->stream_h2d));
-    if (e->stage_buf) HIPCHK(hipFree(e->stage_buf));
-    e->stage_buf = nullptr;
-    HIPCHK(hipMalloc(&e->stage_buf, need));
-    e->stage_bytes = need;
+    if (e->stage_buf.reserve(need)) return DRB_EDEVICE;
   }
-  uint8_t *d = (uint8_t *)e->stage_buf;
+  uint8_t *d = e->stage_buf.as<uint8_t>();
   // the previous call's arrays are read once its upload is done
   if (async) HIPCHK(hipEventSynchronize(e->ev_uploaded));
   // the upload and the layout on the copy stream: the upload overlaps the
@@ -1383,8 +1359,9 @@ static int stage_packed(drb_engine *e, uint32_t slot, uint32_t type,
         d + o_tmp, tb2, WidenU16(l16, WidenU32()), off, (int)n, ls));
   k_stage_packed<<<(unsigned)((G + 255) / 256), 256, 0, ls>>>(
       v, slot, type, d + o_cnt, e0, (const uint64_t *)(d + o_key),
-      client_ids ? (const uint64_t *)(d + o_cid) : nullptr, e->sess_client,
-      l16, off, d + o_pool, (uint64_t)pool_len);
+      client_ids ? (const uint64_t *)(d + o_cid) : nullptr,
+      e->sess_client.as<uint64_t>(), l16, off, d + o_pool,
+      (uint64_t)pool_len);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(e->ev_staged, ls));
   HIPCHK(hipEventRecord(e->ev_stage_free, ls));
@@ -1414,14 +1391,15 @@ extern "C" int drb_set_session_clients(drb_engine *e,
   if (!e || !client_ids) return DRB_EINVAL;
   const uint64_t G = e->v.G;
   HIPCHK(hipSetDevice(e->cfg.device));
-  if (!e->sess_client) {
+  if (!e->sess_client.p) {
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMalloc(&e->sess_client, std::max<uint64_t>(G, 1) * 8));
+    if (e->sess_client.reserve(std::max<uint64_t>(G, 1) * 8))
+      return DRB_EDEVICE;
     e->bytes += G * 8;
   }
   // ordered before every later staging and export (both streams wait)
   HIPCHK(hipStreamSynchronize(e->stream_h2d));
-  HIPCHK(hipMemcpyAsync(e->sess_client, client_ids, G * 8,
+  HIPCHK(hipMemcpyAsync(e->sess_client.p, client_ids, G * 8,
                         hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return DRB_OK;
@@ -4244,50 +4222,31 @@ extern "C" int drb_recover_tan(drb_engine *e, const drb_recover_in *in,
       files[k] = RecFile{f.off, f.len, f.log, 0};
     }
   }
-  uint8_t *dbytes = nullptr;
-  RecFile *dfiles = nullptr;
-  uint32_t *dfirst = nullptr;
-  TrPlan *dplans = nullptr;
-  drb_recover_status *dst = nullptr;
-  auto release = [&]() {
-    (void)hipFree(dbytes);
-    (void)hipFree(dfiles);
-    (void)hipFree(dfirst);
-    (void)hipFree(dplans);
-    (void)hipFree(dst);
-  };
-  if (hipMalloc((void **)&dbytes, in->n_bytes + 16) != hipSuccess ||
-      hipMalloc((void **)&dfiles, files.size() * sizeof(RecFile)) !=
-          hipSuccess ||
-      hipMalloc((void **)&dfirst, first.size() * sizeof(uint32_t)) !=
-          hipSuccess ||
-      hipMalloc((void **)&dplans, NR * sizeof(TrPlan)) != hipSuccess ||
-      hipMalloc((void **)&dst, NR * sizeof(drb_recover_status)) !=
-          hipSuccess) {
-    release();
+  // (the call's temporaries: freed when it returns, behind run()'s wait)
+  DevBuf dbytes, dfiles, dfirst, dplans, dst;
+  if (dbytes.reserve(in->n_bytes + 16) ||
+      dfiles.reserve(files.size() * sizeof(RecFile)) ||
+      dfirst.reserve(first.size() * sizeof(uint32_t)) ||
+      dplans.reserve(NR * sizeof(TrPlan)) ||
+      dst.reserve(NR * sizeof(drb_recover_status)))
     return DRB_ENOMEM;
-  }
-  int rc = DRB_OK;
   // DRB_RECOVER_TIMING=1 (tools/measure_recover.py): device-event times of
   // the upload and of each pass, one line on stderr
   const char *tenv = getenv("DRB_RECOVER_TIMING");
   const bool timing = tenv && tenv[0] == '1';
-  hipEvent_t tev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  Event tev[5];
   if (timing)
-    for (auto &ev : tev)
-      if (hipEventCreate(&ev) != hipSuccess) {
-        release();
-        return DRB_EDEVICE;
-      }
+    for (Event &ev : tev)
+      if (ev.create(hipEventDefault) != hipSuccess) return DRB_EDEVICE;
   auto run = [&]() -> int {
     if (timing) HIPCHK(hipEventRecord(tev[0], e->stream_h2d));
     for (size_t o = 0; o < in->n_bytes; o += kRecoverPiece)
-      HIPCHK(hipMemcpyAsync(dbytes + o, in->bytes + o,
+      HIPCHK(hipMemcpyAsync(dbytes.as<uint8_t>() + o, in->bytes + o,
                             std::min(kRecoverPiece, in->n_bytes - o),
                             hipMemcpyHostToDevice, e->stream_h2d));
-    HIPCHK(hipMemcpyAsync(dfiles, files.data(), files.size() * sizeof(RecFile),
+    HIPCHK(hipMemcpyAsync(dfiles.p, files.data(), dfiles.cap,
                           hipMemcpyHostToDevice, e->stream_h2d));
-    HIPCHK(hipMemcpyAsync(dfirst, first.data(), first.size() * sizeof(uint32_t),
+    HIPCHK(hipMemcpyAsync(dfirst.p, first.data(), dfirst.cap,
                           hipMemcpyHostToDevice, e->stream_h2d));
     if (timing) HIPCHK(hipEventRecord(tev[1], e->stream_h2d));
     HIPCHK(hipEventRecord(e->ev_staged, e->stream_h2d));
@@ -4295,15 +4254,15 @@ extern "C" int drb_recover_tan(drb_engine *e, const drb_recover_in *in,
     RecParams p;
     p.first_group = in->first_group;
     p.n_groups = in->n_groups;
-    p.bytes = dbytes;
-    p.files = dfiles;
-    p.rep_first = dfirst;
+    p.bytes = dbytes.as<uint8_t>();
+    p.files = dfiles.as<RecFile>();
+    p.rep_first = dfirst.as<uint32_t>();
     p.base_index = in->base_index;
     p.base_term = in->base_term;
     p.seed = in->seed;
     p.qs_base = e->ticks;
-    p.plans = dplans;
-    p.st = dst;
+    p.plans = dplans.as<TrPlan>();
+    p.st = dst.as<drb_recover_status>();
     const unsigned blocks = (unsigned)((NR + REC_BLOCK - 1) / REC_BLOCK);
     if (timing) HIPCHK(hipEventRecord(tev[2], e->stream));
     recover_launch_check(v, p, blocks, e->stream);
@@ -4312,7 +4271,7 @@ extern "C" int drb_recover_tan(drb_engine *e, const drb_recover_in *in,
     recover_launch_place(v, p, blocks, e->stream);
     HIPCHK(hipGetLastError());
     if (timing) HIPCHK(hipEventRecord(tev[4], e->stream));
-    HIPCHK(hipMemcpyAsync(st, dst, NR * sizeof(drb_recover_status),
+    HIPCHK(hipMemcpyAsync(st, dst.p, NR * sizeof(drb_recover_status),
                           hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     if (timing) {
@@ -4327,12 +4286,10 @@ extern "C" int drb_recover_tan(drb_engine *e, const drb_recover_in *in,
     }
     return DRB_OK;
   };
-  rc = run();
-  if (rc) (void)hipStreamSynchronize(e->stream_h2d);
-  if (timing)
-    for (auto &ev : tev) (void)hipEventDestroy(ev);
-  release();
-  if (rc) return rc;
+  if (int rc = run()) {
+    (void)hipStreamSynchronize(e->stream_h2d);
+    return rc;
+  }
   for (uint64_t gi = 0; gi < in->n_groups; ++gi)
     e->recovered[in->first_group + gi] = true;
   return refresh_roles(e);
@@ -4518,14 +4475,8 @@ __global__ void k_batch_values(const View v, uint32_t slot, uint64_t g0,
 }
 
 static int xout(drb_engine *e, size_t bytes, void **p) {
-  if (bytes > e->xout_bytes) {
-    if (e->xout) HIPCHK(hipFree(e->xout));
-    e->xout = nullptr;
-    e->xout_bytes = 0;
-    HIPCHK(hipMalloc(&e->xout, bytes));
-    e->xout_bytes = bytes;
-  }
-  *p = e->xout;
+  if (e->xout.reserve(bytes)) return DRB_EDEVICE;
+  *p = e->xout.p;
   return DRB_OK;
 }
 

@@ -728,50 +728,26 @@ __global__ void k_ing_place(const View v, const uint8_t *s, const DecMsg *dm,
 // C++, also built under AddressSanitizer / UBSan by tests/test_wirehost.py)
 #include "drb_wirehost.hpp"
 
-// device buffers of drb_ingest_wire (grow-only, under ingest_mu)
-struct IngestBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-};
-static int ing_grow(IngestBuf &b, size_t need) {
-  if (need <= b.cap) return DRB_OK;
-  if (b.p) HIPCHK(hipFree(b.p));
-  b.p = nullptr;
-  HIPCHK(hipMalloc(&b.p, need));
-  b.cap = need;
-  return DRB_OK;
-}
 struct IngestState {
-  IngestBuf stream, msgs, ents, sort, misc, chunks, cpu;
+  // device buffers of drb_ingest_wire (grow-only, under ingest_mu)
+  drb::DevBuf stream, msgs, ents, sort, misc, chunks, cpu;
   // the CPU path's messages of the last call, in stream order
   std::vector<drb_wire_cpu> cpu_msgs;
   bool k64_ready = false;     // c_crc_k64 uploaded
-  uint8_t *pinned = nullptr;  // drb_ingest_buffer (hipHostMalloc)
-  size_t pinned_cap = 0;
+  drb::PinnedBuf<hipHostMallocDefault> pinned;  // drb_ingest_buffer
   // the frames' element steps gathered for one DMA (grow-only, pinned)
-  uint32_t *steps = nullptr;
-  size_t steps_cap = 0;
+  drb::PinnedBuf<hipHostMallocDefault> steps;
   // the frames of the last call; their Requests vectors keep their
   // capacity, so a warm call neither faults nor unmaps ~12 B per message
   std::vector<wirehost::Frame> frames;
   // the stream goes up in pieces on its own stream, one event each, so the
   // CRC and count kernels of a piece run while the later pieces upload
-  hipStream_t up = nullptr;
-  std::vector<hipEvent_t> ev;  // per piece: uploaded
-  hipEvent_t evv = nullptr;  // the verdicts' inputs are down (speculation)
+  drb::Stream up;
+  std::vector<drb::Event> ev;  // per piece: uploaded
+  drb::Event evv;  // the verdicts' inputs are down (speculation)
 };
-static void ingest_free(IngestState *st) {
-  if (!st) return;
-  for (hipEvent_t x : st->ev) (void)hipEventDestroy(x);
-  if (st->evv) (void)hipEventDestroy(st->evv);
-  if (st->up) (void)hipStreamDestroy(st->up);
-  if (st->pinned) (void)hipHostFree(st->pinned);
-  if (st->steps) (void)hipHostFree(st->steps);
-  for (IngestBuf *b : {&st->stream, &st->msgs, &st->ents, &st->sort,
-                       &st->misc, &st->chunks, &st->cpu})
-    if (b->p) (void)hipFree(b->p);
-  delete st;
-}
+// (every call of drb_ingest_wire waits for its streams before it returns)
+static void ingest_free(IngestState *st) { delete st; }
 
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -824,14 +800,8 @@ extern "C" int drb_ingest_buffer(drb_engine *e, size_t cap, uint8_t **buf) {
   std::lock_guard<std::mutex> lock(e->ingest_mu);
   if (!e->ingest) e->ingest = new IngestState();
   IngestState &st = *e->ingest;
-  if (cap > st.pinned_cap) {
-    if (st.pinned) HIPCHK(hipHostFree(st.pinned));
-    st.pinned = nullptr;
-    st.pinned_cap = 0;
-    HIPCHK(hipHostMalloc((void **)&st.pinned, cap, hipHostMallocDefault));
-    st.pinned_cap = cap;
-  }
-  *buf = st.pinned;
+  if (st.pinned.reserve(cap)) return DRB_EDEVICE;
+  *buf = st.pinned.as<uint8_t>();
   return DRB_OK;
 }
 
@@ -859,7 +829,7 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
   const size_t walked = wirehost::walk_frames(stream, len, fr, &bad_header);
   tr.mark("headers");
   const size_t sb = al256(walked + 16);
-  if (ing_grow(st.stream, sb)) return DRB_EDEVICE;
+  if (st.stream.reserve(sb)) return DRB_EDEVICE;
   uint8_t *ds = (uint8_t *)st.stream.p;
   hipStream_t sm = e->stream;
   // once the upload is enqueued, every return waits for the engine stream
@@ -907,7 +877,7 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
   }
   cfirst[fr.size()] = (uint32_t)coff.size();
   const size_t nc = coff.size();
-  if (ing_grow(st.chunks, al256(nc * 8 + 8) + 2 * al256(nc * 4 + 4)))
+  if (st.chunks.reserve(al256(nc * 8 + 8) + 2 * al256(nc * 4 + 4)))
     return DRB_EDEVICE;
   uint64_t *d_coff = (uint64_t *)st.chunks.p;
   uint32_t *d_clen = (uint32_t *)((uint8_t *)st.chunks.p + al256(nc * 8 + 8));
@@ -923,14 +893,11 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
   }
   pf.push_back(fr.size());
   const size_t np = pf.size() - 1;
-  if (!st.up &&
-      hipStreamCreateWithFlags(&st.up, hipStreamNonBlocking) != hipSuccess)
-    return DRB_EDEVICE;
+  if (!st.up && st.up.create() != hipSuccess) return DRB_EDEVICE;
   while (st.ev.size() < (np ? np : 1)) {  // (ev[0] also for the start)
-    hipEvent_t x;
-    if (hipEventCreateWithFlags(&x, hipEventDisableTiming) != hipSuccess)
-      return DRB_EDEVICE;
-    st.ev.push_back(x);
+    Event x;
+    if (x.create() != hipSuccess) return DRB_EDEVICE;
+    st.ev.push_back(std::move(x));
   }
   // the upload starts behind what the engine stream has enqueued (the
   // device buffers may still be read by an earlier call)
@@ -985,7 +952,7 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
                     al256(m1 * 4) * 7 + al256(m1) +
                     al256((nf + 1) * 4) + al256((nf + 1) * 8) * 2 +
                     al256(nf + 1) + ING_TALLY_ROWS * 64 + al256(scan_tb);
-  if (ing_grow(st.misc, mb)) return DRB_EDEVICE;
+  if (st.misc.reserve(mb)) return DRB_EDEVICE;
   uint8_t *q = (uint8_t *)st.misc.p;
   auto take = [&](size_t b) {
     uint8_t *r = q;
@@ -1021,19 +988,14 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
     for (size_t f = 0; f < nf; ++f) foff[f] = fr[f].off;
     // the frames' steps into one pinned buffer (host threads, one DMA):
     // per-frame pageable copies ran ~2 ms for a C3 plane's 25 MB
-    if (nm > st.steps_cap) {
-      if (st.steps) HIPCHK(hipHostFree(st.steps));
-      st.steps = nullptr;
-      st.steps_cap = 0;
-      HIPCHK(hipHostMalloc((void **)&st.steps, nm * 4, hipHostMallocDefault));
-      st.steps_cap = nm;
-    }
+    if (st.steps.reserve(nm * 4)) return DRB_EDEVICE;
+    uint32_t *const steps = st.steps.as<uint32_t>();
     // 2 B steps when every one fits (a message under 64 KB), else 4 B
     std::atomic<bool> wide{false};
     {
       const size_t nt = std::min<size_t>(16, nf);
       std::vector<std::thread> th;
-      uint16_t *s16 = (uint16_t *)st.steps;
+      uint16_t *s16 = (uint16_t *)steps;
       for (size_t t = 0; t < nt; ++t)
         th.emplace_back([&, t]() {
           for (size_t f = t; f < nf && !wide.load(std::memory_order_relaxed);
@@ -1050,7 +1012,7 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
         th.emplace_back([&, t]() {
           for (size_t f = t; f < nf; f += nt)
             if (!fr[f].step.empty())
-              memcpy(st.steps + mbase[f], fr[f].step.data(),
+              memcpy(steps + mbase[f], fr[f].step.data(),
                      fr[f].step.size() * 4);
         });
       for (auto &x : th) x.join();
@@ -1060,7 +1022,7 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
     // queued here waits on the copy engine behind the stream's remaining
     // pieces, and the per-piece counts below need it (profiles/r04_ingest)
     void *hsteps = nullptr;
-    if (hipHostGetDevicePointer(&hsteps, st.steps, 0) == hipSuccess &&
+    if (hipHostGetDevicePointer(&hsteps, steps, 0) == hipSuccess &&
         hsteps && ((uintptr_t)hsteps & 15) == 0) {
       const uint64_t nv = step_bytes / 16 + 1;
       k_zc_pull<<<(unsigned)std::min<uint64_t>(1024, (nv + 1023) / 1024), 256,
@@ -1069,7 +1031,7 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
       HIPCHK(hipGetLastError());
     } else {
       (void)hipGetLastError();
-      HIPCHK(hipMemcpyAsync(d_step, st.steps, step_bytes,
+      HIPCHK(hipMemcpyAsync(d_step, steps, step_bytes,
                             hipMemcpyHostToDevice, sm));
     }
     HIPCHK(hipMemcpyAsync(d_mbase, mbase.data(), (nf + 1) * 8,
@@ -1084,7 +1046,7 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
         d_step, d_step64, nm, !wide);
     HIPCHK(hipcub::DeviceScan::InclusiveSum(d_scan_tmp, scan_tb, d_step64,
                                             d_scan, (int)nm, sm));
-    if (ing_grow(st.msgs, al256(nm * sizeof(DecMsg)))) return DRB_EDEVICE;
+    if (st.msgs.reserve(al256(nm * sizeof(DecMsg)))) return DRB_EDEVICE;
   }
   // sort / scan temporary storage and the key arrays (the speculative
   // pass below uses them per piece)
@@ -1100,7 +1062,7 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
                                             (int)nm, sm));
     tb = std::max(tb, tb2);
     const size_t sbytes = al256(nm * 4) * 4 + al256(tb);
-    if (ing_grow(st.sort, sbytes)) return DRB_EDEVICE;
+    if (st.sort.reserve(sbytes)) return DRB_EDEVICE;
     sp = (uint8_t *)st.sort.p;
     tmp = sp + 4 * al256(nm * 4);
     kin = (uint32_t *)sp;
@@ -1172,9 +1134,7 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
     // the verdicts
     HIPCHK(hipMemcpyAsync(rows, d_ctr, sizeof(rows), hipMemcpyDeviceToHost,
                           sm));
-    if (!st.evv &&
-        hipEventCreateWithFlags(&st.evv, hipEventDisableTiming) != hipSuccess)
-      return DRB_EDEVICE;
+    if (!st.evv && st.evv.create() != hipSuccess) return DRB_EDEVICE;
     HIPCHK(hipEventRecord(st.evv, sm));
     HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, kin, kout, vin, vout,
                                               (int)nm, 0, kbits, sm));
@@ -1246,7 +1206,7 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
     res.dropped += c0[4];
     const uint64_t tot = c0[5];
     // the CPU path's messages: InstallSnapshots, and what placement diverts
-    if (ing_grow(st.cpu, al256(8) + nm * sizeof(drb_wire_cpu)))
+    if (st.cpu.reserve(al256(8) + nm * sizeof(drb_wire_cpu)))
       return DRB_EDEVICE;
     unsigned long long *d_cpu_n = (unsigned long long *)st.cpu.p;
     drb_wire_cpu *d_cpu = (drb_wire_cpu *)((uint8_t *)st.cpu.p + al256(8));
@@ -1257,7 +1217,7 @@ extern "C" int drb_ingest_wire(drb_engine *e, const uint8_t *stream,
     if (any_deliver) {
       if (!spec_ok) {
         const size_t eb = al256((tot ? tot : 1) * sizeof(drb_entry));
-        if (ing_grow(st.ents, eb)) return DRB_EDEVICE;
+        if (st.ents.reserve(eb)) return DRB_EDEVICE;
         k_ing_decode<<<(unsigned)((nm + 255) / 256), 256, 0, sm>>>(
             ds, d_moff, d_mlen, d_ent0, d_nsc, dm, (drb_entry *)st.ents.p, nm,
             cmd_cap, st.ents.cap / sizeof(drb_entry), d_ctr, 0);

@@ -741,23 +741,19 @@ __global__ void k_wire_finish(const WireArgs a, const uint8_t *src,
 // ------------------------------------------------------------ host side
 struct WireState {
   uint64_t G = 0;
-  uint64_t *cnt = nullptr, *bytes = nullptr, *upper = nullptr;
-  uint64_t *bsum = nullptr, *tot = nullptr;
-  drb::WireFrame *frames = nullptr;
-  drb::WirePlan *plan = nullptr;
-  uint8_t *src = nullptr;
-  uint8_t *out = nullptr;
-  uint64_t out_cap = 0, out_len = 0, n_frames = 0;
+  drb::DevBuf cnt, bytes, upper;  // uint64_t [G]
+  drb::DevBuf bsum, tot;          // the scan's block sums and totals
+  drb::DevBuf frames;             // WireFrame [WIRE_MAX_FRAMES]
+  drb::DevBuf plan;               // WirePlan
+  drb::DevBuf src;                // the source address
+  drb::DevBuf out;                // the encoded stream (grow-only)
+  uint64_t out_len = 0, n_frames = 0;
 };
+// (the u64 arrays of the scans)
+static uint64_t *u64p(const drb::DevBuf &b) { return b.as<uint64_t>(); }
 
 static void wire_free(drb_engine *e) {
-  WireState *w = e->wire;
-  if (!w) return;
-  void *ps[] = {w->cnt, w->bytes, w->upper, w->bsum, w->tot,
-                w->frames, w->plan, w->src, w->out};
-  for (void *p : ps)
-    if (p) (void)hipFree(p);
-  delete w;
+  delete e->wire;
   e->wire = nullptr;
 }
 
@@ -786,19 +782,18 @@ static int wire_init(drb_engine *e) {
     wire_tables_ready = 1;
   }
   if (e->wire) return DRB_OK;
-  WireState *w = new WireState();
-  e->wire = w;
+  std::unique_ptr<WireState> w(new WireState());
   const uint64_t G = e->cfg.num_groups;
   const uint64_t nb = (G + drb::SCAN_TILE - 1) / drb::SCAN_TILE;
   w->G = G;
-  HIPCHK(hipMalloc(&w->cnt, G * 8));
-  HIPCHK(hipMalloc(&w->bytes, G * 8));
-  HIPCHK(hipMalloc(&w->upper, G * 8));
-  HIPCHK(hipMalloc(&w->bsum, (nb + 1) * 3 * 8));
-  HIPCHK(hipMalloc(&w->tot, 4 * 8));
-  HIPCHK(hipMalloc(&w->frames, drb::WIRE_MAX_FRAMES * sizeof(drb::WireFrame)));
-  HIPCHK(hipMalloc(&w->plan, sizeof(drb::WirePlan)));
-  HIPCHK(hipMalloc(&w->src, drb::WIRE_MAX_SRC));
+  if (w->cnt.reserve(G * 8) || w->bytes.reserve(G * 8) ||
+      w->upper.reserve(G * 8) || w->bsum.reserve((nb + 1) * 3 * 8) ||
+      w->tot.reserve(4 * 8) ||
+      w->frames.reserve(drb::WIRE_MAX_FRAMES * sizeof(drb::WireFrame)) ||
+      w->plan.reserve(sizeof(drb::WirePlan)) ||
+      w->src.reserve(drb::WIRE_MAX_SRC))
+    return DRB_EDEVICE;
+  e->wire = w.release();  // published complete, or not at all
   return DRB_OK;
 }
 
@@ -816,6 +811,10 @@ extern "C" int drb_encode_wire(drb_engine *e, uint32_t from_slot,
   int rc = wire_init(e);
   if (rc) return rc;
   WireState *w = e->wire;
+  uint64_t *const cnt = u64p(w->cnt), *const bytes = u64p(w->bytes),
+                 *const upper = u64p(w->upper), *const bsum = u64p(w->bsum);
+  drb::WireFrame *const frames = w->frames.as<drb::WireFrame>();
+  drb::WirePlan *const dplan = w->plan.as<drb::WirePlan>();
   w->out_len = w->n_frames = 0;
   if (res) memset(res, 0, sizeof(*res));
   if (e->round == 0) return DRB_OK;  // nothing sent yet
@@ -833,41 +832,37 @@ extern "C" int drb_encode_wire(drb_engine *e, uint32_t from_slot,
   a.trailer = 1 + drb::sov64(a.deployment_id) + 1 + drb::sov64(a.src_len) +
               a.src_len + 1 + drb::sov64(a.bin_ver);
   if (a.src_len)
-    HIPCHK(hipMemcpyAsync(w->src, cfg->source_address, a.src_len,
+    HIPCHK(hipMemcpyAsync(w->src.p, cfg->source_address, a.src_len,
                           hipMemcpyHostToDevice, e->stream));
   const uint64_t G = w->G;
   const unsigned gb = (unsigned)((G + 255) / 256);
-  drb::k_wire_measure<<<gb, 256, 0, e->stream>>>(e->v, a, w->cnt, w->bytes,
-                                                 w->upper);
+  drb::k_wire_measure<<<gb, 256, 0, e->stream>>>(e->v, a, cnt, bytes, upper);
   HIPCHK(hipGetLastError());
   const uint64_t nb = (G + drb::SCAN_TILE - 1) / drb::SCAN_TILE;
-  drb::k_scan3_up<<<(unsigned)nb, 256, 0, e->stream>>>(w->cnt, w->bytes,
-                                                       w->upper, G, w->bsum);
-  drb::k_scan3_top<<<1, 256, 0, e->stream>>>(w->bsum, nb, w->tot);
-  drb::k_scan3_down<<<(unsigned)nb, 256, 0, e->stream>>>(w->cnt, w->bytes,
-                                                         w->upper, G, w->bsum);
-  drb::k_wire_plan<<<1, 64, 0, e->stream>>>(e->v, a, w->cnt, w->bytes,
-                                           w->upper, w->tot, w->frames,
-                                           w->plan);
+  drb::k_scan3_up<<<(unsigned)nb, 256, 0, e->stream>>>(cnt, bytes, upper, G,
+                                                       bsum);
+  drb::k_scan3_top<<<1, 256, 0, e->stream>>>(bsum, nb, u64p(w->tot));
+  drb::k_scan3_down<<<(unsigned)nb, 256, 0, e->stream>>>(cnt, bytes, upper, G,
+                                                         bsum);
+  drb::k_wire_plan<<<1, 64, 0, e->stream>>>(e->v, a, cnt, bytes, upper,
+                                           u64p(w->tot), frames, dplan);
   HIPCHK(hipGetLastError());
   drb::WirePlan plan;
-  HIPCHK(hipMemcpyAsync(&plan, w->plan, sizeof(plan), hipMemcpyDeviceToHost,
+  HIPCHK(hipMemcpyAsync(&plan, dplan, sizeof(plan), hipMemcpyDeviceToHost,
                         e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   if (plan.overflow) return DRB_ERANGE;
-  if (plan.total_bytes > w->out_cap) {
-    if (w->out) HIPCHK(hipFree(w->out));
-    w->out = nullptr;
-    const uint64_t cap = (plan.total_bytes + (1 << 20)) & ~15ull;
-    HIPCHK(hipMalloc(&w->out, cap));
-    w->out_cap = cap;
-  }
+  if (plan.total_bytes > w->out.cap &&
+      w->out.reserve((plan.total_bytes + (1 << 20)) & ~15ull))
+    return DRB_EDEVICE;
+  uint8_t *const out = w->out.as<uint8_t>();
   if (plan.n_frames) {
-    drb::k_wire_encode<<<gb, 256, 0, e->stream>>>(e->v, a, w->cnt, w->bytes,
-                                                  w->frames, w->plan, w->out);
+    drb::k_wire_encode<<<gb, 256, 0, e->stream>>>(e->v, a, cnt, bytes, frames,
+                                                  dplan, out);
     HIPCHK(hipGetLastError());
     drb::k_wire_finish<<<(unsigned)((plan.n_frames + 63) / 64), 64, 0,
-                         e->stream>>>(a, w->src, w->frames, w->plan, w->out);
+                         e->stream>>>(a, w->src.as<uint8_t>(), frames,
+                                      dplan, out);
     HIPCHK(hipGetLastError());
   }
   w->out_len = plan.total_bytes;
@@ -883,7 +878,7 @@ extern "C" int drb_encode_wire(drb_engine *e, uint32_t from_slot,
 extern "C" int drb_wire_buffer(drb_engine *e, const uint8_t **dev,
                                uint64_t *len) {
   if (!e || !dev || !len) return DRB_EINVAL;
-  *dev = e->wire ? e->wire->out : nullptr;
+  *dev = e->wire ? e->wire->out.as<uint8_t>() : nullptr;
   *len = e->wire ? e->wire->out_len : 0;
   return DRB_OK;
 }
@@ -895,7 +890,7 @@ extern "C" int drb_export_wire(drb_engine *e, uint8_t *out, size_t cap,
   if (len) *len = n;
   if (n > cap) return DRB_ERANGE;
   if (n) {
-    HIPCHK(hipMemcpyAsync(out, e->wire->out, n, hipMemcpyDeviceToHost,
+    HIPCHK(hipMemcpyAsync(out, e->wire->out.p, n, hipMemcpyDeviceToHost,
                           e->stream));
   }
   HIPCHK(hipStreamSynchronize(e->stream));

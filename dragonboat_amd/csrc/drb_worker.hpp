@@ -39,27 +39,28 @@
 constexpr int kWorkerSets = 16;
 
 struct WorkerSet {
-  hipEvent_t ev_staged = nullptr, ev_drained = nullptr;
-  uint32_t *lanes = nullptr;  // [G]
-  uint32_t *rd = nullptr;     // ctx tags
-  uint32_t *val = nullptr;
-  uint32_t *meta = nullptr;   // 2-bit codes, 16 per word
-  uint64_t *dfr = nullptr;    // deferred ReadyToReads' Index
-  uint64_t cap_rd = 0, cap_val = 0, cap_df = 0;  // staging capacity
+  drb::Event ev_staged, ev_drained;
+  // the staging (grow-only; a buffer's capacity is its DevBuf's)
+  drb::DevBuf lanes;  // uint32_t [G]
+  drb::DevBuf rd;     // uint32_t ctx tags
+  drb::DevBuf val;    // uint32_t
+  drb::DevBuf meta;   // uint32_t 2-bit codes, 16 per word
+  drb::DevBuf dfr;    // uint64_t deferred ReadyToReads' Index
   // the buffers of the export in flight (waited for or not)
   const drb_worker_bufs *owner = nullptr;
   bool issued = false;  // the copies of its job issued
   int err = 0;          // a failed copy (reported and cleared by its wait)
-  hsa_signal_t done{0};  // copies outstanding (HSA)
+  drb::Signal done;     // copies outstanding (HSA)
 };
 
 struct WorkerState {
-  hipStream_t sx = nullptr;  // the drain thread's copies
+  drb::Stream sx;  // the drain thread's copies
   WorkerSet set[kWorkerSets];
-  uint4 *cnt = nullptr, *off = nullptr;  // [G + 1]
-  void *tmp = nullptr;
+  drb::DevBuf cnt, off;  // uint4 [G + 1]
+  drb::DevBuf tmp;       // the scan's temporary storage
   size_t tmp_bytes = 0;
-  unsigned long long *hdr = nullptr;      // pinned, mapped [sets][4]: totals
+  // pinned, mapped unsigned long long [sets][4]: the totals
+  drb::PinnedBuf<hipHostMallocMapped> hdr;
   unsigned long long *hdr_dev = nullptr;  // ... its device address
   // the drain thread: one job per export, in order
   struct Job {
@@ -80,7 +81,7 @@ struct WorkerState {
 // until the copies of staging set k are done
 static void worker_wait_copies(WorkerState &w, int k) {
   // (a set never used has no signal yet: nothing to wait for)
-  if (!w.hsa || !w.set[k].done.handle) return;
+  if (!w.hsa || !w.set[k].done) return;
   while (hsa_signal_wait_scacquire(w.set[k].done, HSA_SIGNAL_CONDITION_LT, 1,
                                    UINT64_MAX, HSA_WAIT_STATE_BLOCKED) >= 1) {
   }
@@ -253,25 +254,7 @@ static void worker_free(drb_engine *e) {
     w->th.join();
   }
   if (w->sx) (void)hipStreamSynchronize(w->sx);
-  for (int k = 0; k < kWorkerSets; ++k) {
-    WorkerSet &s = w->set[k];
-    if (w->hsa) {
-      worker_wait_copies(*w, k);
-      if (s.done.handle) (void)hsa_signal_destroy(s.done);
-    }
-    if (s.ev_staged) (void)hipEventDestroy(s.ev_staged);
-    if (s.ev_drained) (void)hipEventDestroy(s.ev_drained);
-    if (s.lanes) (void)hipFree(s.lanes);
-    if (s.rd) (void)hipFree(s.rd);
-    if (s.val) (void)hipFree(s.val);
-    if (s.meta) (void)hipFree(s.meta);
-    if (s.dfr) (void)hipFree(s.dfr);
-  }
-  if (w->cnt) (void)hipFree(w->cnt);
-  if (w->off) (void)hipFree(w->off);
-  if (w->tmp) (void)hipFree(w->tmp);
-  if (w->hdr) (void)hipHostFree(w->hdr);
-  if (w->sx) (void)hipStreamDestroy(w->sx);
+  for (int k = 0; k < kWorkerSets; ++k) worker_wait_copies(*w, k);
   delete w;
   e->worker = nullptr;
 }
@@ -284,7 +267,7 @@ static hipError_t worker_copy(drb_engine *e, WorkerState &w,
   WorkerSet &s = w.set[k];
   hipError_t r = hipEventSynchronize(s.ev_staged);
   if (r != hipSuccess) return r;
-  const unsigned long long *t = w.hdr + 4 * k;
+  const unsigned long long *t = w.hdr.as<unsigned long long>() + 4 * k;
   const uint64_t nrd = std::min<uint64_t>(t[0], j.b.reads_cap);
   const uint64_t nval = std::min<uint64_t>(t[1], j.b.values_cap);
   const uint64_t ndf = std::min<uint64_t>(t[2], j.b.deferred_cap);
@@ -292,11 +275,11 @@ static hipError_t worker_copy(drb_engine *e, WorkerState &w,
     void *dst;
     const void *src;
     size_t n;
-  } cp[5] = {{j.b.lanes, s.lanes, (size_t)j.np * 4},
-             {j.b.reads, s.rd, nrd * 4},
-             {j.b.values, s.val, nval * 4},
-             {j.b.value_meta, s.meta, (nval + 3) / 4},
-             {j.b.deferred, s.dfr, ndf * 8}};
+  } cp[5] = {{j.b.lanes, s.lanes.p, (size_t)j.np * 4},
+             {j.b.reads, s.rd.p, nrd * 4},
+             {j.b.values, s.val.p, nval * 4},
+             {j.b.value_meta, s.meta.p, (nval + 3) / 4},
+             {j.b.deferred, s.dfr.p, ndf * 8}};
   if (w.hsa) {
     const HsaXfer &x = e->xfer;
     int n = 0;
@@ -320,8 +303,8 @@ static hipError_t worker_copy(drb_engine *e, WorkerState &w,
   return r;
 }
 
-static void worker_thread(drb_engine *e) {
-  WorkerState &w = *e->worker;
+static void worker_thread(drb_engine *e, WorkerState *ws) {
+  WorkerState &w = *ws;
   (void)hipSetDevice(e->cfg.device);  // (the current device is per thread)
   for (;;) {
     WorkerState::Job j;
@@ -352,63 +335,51 @@ static uint64_t worker_meta_words(uint64_t cval) {
 static int worker_reserve(drb_engine *e, int k, uint64_t crd, uint64_t cval,
                           uint64_t cdf) {
   WorkerSet &s = e->worker->set[k];
-  if (!s.ev_staged)
-    HIPCHK(hipEventCreateWithFlags(&s.ev_staged, hipEventDisableTiming));
-  if (!s.ev_drained)
-    HIPCHK(hipEventCreateWithFlags(&s.ev_drained, hipEventDisableTiming));
-  if (!s.lanes)
-    HIPCHK(hipMalloc(&s.lanes, std::max<uint64_t>(e->v.G, 1) * 4 + 16));
-  if (e->worker->hsa && !s.done.handle &&
-      hsa_signal_create(0, 0, nullptr, &s.done) != HSA_STATUS_SUCCESS) {
-    s.done.handle = 0;
+  if (!s.ev_staged) HIPCHK(s.ev_staged.create());
+  if (!s.ev_drained) HIPCHK(s.ev_drained.create());
+  if (s.lanes.reserve(std::max<uint64_t>(e->v.G, 1) * 4 + 16))
     return DRB_EDEVICE;
-  }
-  if (s.rd && crd <= s.cap_rd && cval <= s.cap_val && cdf <= s.cap_df)
+  if (e->worker->hsa && !s.done && s.done.create() != HSA_STATUS_SUCCESS)
+    return DRB_EDEVICE;
+  const size_t brd = std::max<uint64_t>(crd, 1) * 4 + 16,
+               bval = std::max<uint64_t>(cval, 1) * 4 + 16,
+               bmeta = worker_meta_words(cval) * 4,
+               bdf = std::max<uint64_t>(cdf, 1) * 8 + 16;
+  if (brd <= s.rd.cap && bval <= s.val.cap && bmeta <= s.meta.cap &&
+      bdf <= s.dfr.cap)
     return DRB_OK;
   // (the engine stream's earlier exports may still read the old staging)
   HIPCHK(hipStreamSynchronize(e->stream));
-  crd = std::max(crd, s.cap_rd);
-  cval = std::max(cval, s.cap_val);
-  cdf = std::max(cdf, s.cap_df);
-  if (s.rd) HIPCHK(hipFree(s.rd));
-  if (s.val) HIPCHK(hipFree(s.val));
-  if (s.meta) HIPCHK(hipFree(s.meta));
-  if (s.dfr) HIPCHK(hipFree(s.dfr));
-  s.rd = nullptr;
-  s.val = nullptr;
-  s.meta = nullptr;
-  s.dfr = nullptr;
-  HIPCHK(hipMalloc(&s.rd, std::max<uint64_t>(crd, 1) * 4 + 16));
-  HIPCHK(hipMalloc(&s.val, std::max<uint64_t>(cval, 1) * 4 + 16));
-  HIPCHK(hipMalloc(&s.meta, worker_meta_words(cval) * 4));
-  HIPCHK(hipMalloc(&s.dfr, std::max<uint64_t>(cdf, 1) * 8 + 16));
-  s.cap_rd = crd;
-  s.cap_val = cval;
-  s.cap_df = cdf;
+  if (s.rd.reserve(brd) || s.val.reserve(bval) || s.meta.reserve(bmeta) ||
+      s.dfr.reserve(bdf))
+    return DRB_EDEVICE;
   return DRB_OK;
 }
 
 static int worker_init(drb_engine *e) {
   if (e->worker) return DRB_OK;
-  WorkerState *w = new WorkerState();
-  e->worker = w;
+  std::unique_ptr<WorkerState> w(new WorkerState());
   const uint64_t G = e->v.G;
   HIPCHK(hipSetDevice(e->cfg.device));
-  HIPCHK(hipStreamCreateWithFlags(&w->sx, hipStreamNonBlocking));
-  HIPCHK(hipMalloc(&w->cnt, (G + 1) * sizeof(uint4)));
-  HIPCHK(hipMalloc(&w->off, (G + 1) * sizeof(uint4)));
-  HIPCHK(hipcub::DeviceScan::ExclusiveScan(nullptr, w->tmp_bytes, w->cnt,
-                                           w->off, U4Sum(),
+  HIPCHK(w->sx.create());
+  if (w->cnt.reserve((G + 1) * sizeof(uint4)) ||
+      w->off.reserve((G + 1) * sizeof(uint4)))
+    return DRB_EDEVICE;
+  HIPCHK(hipcub::DeviceScan::ExclusiveScan(nullptr, w->tmp_bytes,
+                                           w->cnt.as<uint4>(),
+                                           w->off.as<uint4>(), U4Sum(),
                                            make_uint4(0, 0, 0, 0),
                                            (int)(G + 1), e->stream));
-  HIPCHK(hipMalloc(&w->tmp, std::max<size_t>(w->tmp_bytes, 16)));
   const size_t hb = 4 * kWorkerSets * sizeof(unsigned long long);
-  HIPCHK(hipHostMalloc((void **)&w->hdr, hb, hipHostMallocMapped));
-  memset(w->hdr, 0, hb);
-  HIPCHK(hipHostGetDevicePointer((void **)&w->hdr_dev, w->hdr, 0));
+  if (w->tmp.reserve(std::max<size_t>(w->tmp_bytes, 16)) ||
+      w->hdr.reserve(hb))
+    return DRB_EDEVICE;
+  memset(w->hdr.p, 0, hb);
+  HIPCHK(hipHostGetDevicePointer((void **)&w->hdr_dev, w->hdr.p, 0));
   // the copies on the engine's download SDMA engine (drb_hsa.hpp)
   w->hsa = hsa_xfer_init(e->cfg.device, &e->xfer);
-  w->th = std::thread(worker_thread, e);
+  w->th = std::thread(worker_thread, e, w.get());
+  e->worker = w.release();  // published complete: the drain thread runs
   return DRB_OK;
 }
 
@@ -494,18 +465,21 @@ extern "C" int drb_worker_export_part(drb_engine *e, uint32_t slot,
       v.read_res && e->reads_round == e->round ? e->reads_n : 0u;
   const unsigned blocks = (unsigned)((np + 1 + 255) / 256);
   k_worker_count<<<blocks, 256, 0, e->stream>>>(v, slot, n_reads, g0,
-                                                n_parts, np, w.cnt);
+                                                n_parts, np,
+                                                w.cnt.as<uint4>());
   size_t tb = w.tmp_bytes;
   if (hipGetLastError() != hipSuccess ||
-      hipcub::DeviceScan::ExclusiveScan(w.tmp, tb, w.cnt, w.off, U4Sum(),
+      hipcub::DeviceScan::ExclusiveScan(w.tmp.p, tb, w.cnt.as<uint4>(),
+                                        w.off.as<uint4>(), U4Sum(),
                                         make_uint4(0, 0, 0, 0), (int)(np + 1),
                                         e->stream) != hipSuccess ||
-      hipMemsetAsync(s.meta, 0, worker_meta_words(s.cap_val) * 4,
-                     e->stream) != hipSuccess)
+      hipMemsetAsync(s.meta.p, 0, s.meta.cap, e->stream) != hipSuccess)
     return release(DRB_EDEVICE);
   k_worker_compact<<<blocks, 256, 0, e->stream>>>(
-      v, slot, n_reads, g0, n_parts, np, e->sess_client, w.off, s.lanes, s.rd,
-      b->reads_cap, s.val, s.meta, b->values_cap, s.dfr, b->deferred_cap,
+      v, slot, n_reads, g0, n_parts, np, e->sess_client.as<uint64_t>(),
+      w.off.as<uint4>(), s.lanes.as<uint32_t>(), s.rd.as<uint32_t>(),
+      b->reads_cap, s.val.as<uint32_t>(), s.meta.as<uint32_t>(),
+      b->values_cap, s.dfr.as<uint64_t>(), b->deferred_cap,
       w.hdr_dev + 4 * k);
   if (hipGetLastError() != hipSuccess ||
       hipEventRecord(s.ev_staged, e->stream) != hipSuccess)
@@ -550,9 +524,10 @@ extern "C" int drb_worker_wait(drb_engine *e, drb_worker_bufs *b) {
       return err;
     }
   }
-  b->n_reads = w.hdr[4 * k];
-  b->n_values = w.hdr[4 * k + 1];
-  b->n_deferred = w.hdr[4 * k + 2];
+  const unsigned long long *t = w.hdr.as<unsigned long long>() + 4 * k;
+  b->n_reads = t[0];
+  b->n_values = t[1];
+  b->n_deferred = t[2];
   {
     std::lock_guard<std::mutex> g(w.mu);
     s.owner = nullptr;

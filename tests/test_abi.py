@@ -154,3 +154,23 @@ def test_create_rejects_invalid_config(kw):
     with pytest.raises(engine.DrbError) as ei:
         engine.Engine(**kw)
     assert "status %d" % abi.DRB_EINVAL in str(ei.value)
+
+
+@pytest.mark.parametrize("kw,status", [
+    # the ranks' groups cover total_groups
+    (dict(num_groups=64, num_replicas=3, total_groups=65), abi.DRB_EINVAL),
+    # overflow buckets are linked by 32-bit number
+    (dict(num_groups=64, num_replicas=3, kv_overflow_buckets=0xffffffff),
+     abi.DRB_ERANGE),
+    # the multiplexed tan stages 256 records of save_cap bytes per log for
+    # 64 groups: past 4 GiB
+    (dict(num_groups=64, num_replicas=3, save_tan=1, tan_multiplexed=1,
+          save_cap=1 << 25), abi.DRB_ERANGE),
+])
+def test_create_rejects_with_status(kw, status):
+    """The checks that once ran after the streams, the events and part of
+    the device arrays existed: each answers with its own status before a
+    device is touched (without a GPU the answer is not DRB_EDEVICE)."""
+    with pytest.raises(engine.DrbError) as ei:
+        engine.Engine(**kw)
+    assert "status %d" % status in str(ei.value)
