@@ -35,198 +35,12 @@
 #include <atomic>
 #include <thread>
 
+// Message.Unmarshal and the colfer Entry (DecMsg, ING_*, d_message): plain
+// C++ shared with the host, also built under AddressSanitizer / UBSan by
+// tests/test_msgdecode_host.py
+#include "drb_msgdec.hpp"
+
 namespace drb {
-
-// one decoded pb.Message (raftpb/message.go:6-20) of an ingested stream
-struct DecMsg {
-  uint64_t shard, from, to, term, log_term, log_index, commit, hint,
-      hint_high;
-  uint64_t ent0;   // its first entry in the decoded entry array
-  uint32_t type, reject, n_ent, err;  // err: ING_*
-};
-constexpr uint32_t ING_OK = 0, ING_BAD = 1, ING_SNAPSHOT = 2, ING_BIG = 3;
-
-// A lane's byte cursor over the uploaded stream: one load per byte, which
-// hit the L1 (a 16 B register window measured 2-4 % slower on the C3
-// plane, profiles/r04_ingest)
-struct Bytes {
-  const uint8_t *p;
-  __device__ explicit Bytes(const uint8_t *d) : p(d) {}
-  __device__ inline uint32_t operator[](uint64_t i) const { return p[i]; }
-};
-
-// (every index below is from the message's first byte; d_entry's from the
-// entry's, at offset e0)
-template <class B>
-__device__ inline bool d_varint(B &d, uint32_t n, uint32_t &i,
-                                uint64_t &v) {
-  v = 0;
-  for (uint32_t s = 0; s < 70; s += 7) {
-    if (i >= n) return false;
-    const uint32_t b = d[i++];
-    v |= (uint64_t)(b & 0x7fu) << s;
-    if (b < 0x80u) return true;
-  }
-  return false;
-}
-
-// skipRaft (raft.pb.go): an unknown field
-template <class B>
-__device__ inline bool d_skip(B &d, uint32_t n, uint32_t &i,
-                              uint64_t wire) {
-  uint64_t x;
-  switch (wire & 7) {
-    case 0: return d_varint(d, n, i, x);
-    case 1: i += 8; return i <= n;
-    case 2:
-      if (!d_varint(d, n, i, x) || x > n - i) return false;
-      i += (uint32_t)x;
-      return true;
-    case 5: i += 4; return i <= n;
-    default: return false;  // groups are not used by raftpb
-  }
-}
-
-// colfer u64 field body (raft_optimized.go:316-350): varint whose 9th
-// byte is taken whole, or 8 bytes big endian after a 0x80-flagged tag
-template <class B>
-__device__ inline bool d_colfer_u64(B &d, uint32_t e0, uint32_t n,
-                                    uint32_t &i, bool flag, uint64_t &v) {
-  if (flag) {
-    if (i + 8 >= n) return false;
-    v = 0;
-    for (int k = 0; k < 8; ++k) v = (v << 8) | d[e0 + i + k];
-    i += 8;
-    return true;
-  }
-  v = 0;
-  for (uint32_t s = 0;; s += 7) {
-    if (i + 1 >= n) return false;
-    const uint64_t b = d[e0 + i++];
-    if (s == 56 || b < 0x80) {
-      v |= b << s;
-      return true;
-    }
-    v |= (b & 0x7f) << s;
-  }
-}
-
-// colfer Entry.Unmarshal (raft_optimized.go:308-656) of the n bytes at e0;
-// cmd_off is the Cmd's offset from e0
-template <class B>
-__device__ inline bool d_entry(B &d, uint32_t e0, uint32_t n,
-                               drb_entry &e) {
-  e.term = e.index = e.key = e.client_id = e.series_id = e.responded_to = 0;
-  e.type = e.cmd_len = 0;
-  e.cmd_off = 0;
-  if (n == 0) return false;
-  uint32_t i = 1;
-  uint32_t h = d[e0];
-  for (uint32_t tag = 0; tag < 7; ++tag) {
-    if ((h & 0x7fu) != tag || h == 0x7fu) continue;
-    if (tag == 2) {  // Type: uint32 varint, 0x80 flag = negated
-      uint64_t x = 0;
-      for (uint32_t s = 0;; s += 7) {
-        if (i + 1 >= n) return false;
-        const uint64_t b = d[e0 + i++];
-        x |= (b & 0x7f) << s;
-        if (b < 0x80) break;
-        if (s > 28) return false;
-      }
-      e.type = (h & 0x80u) ? (uint32_t)(~(uint32_t)x + 1) : (uint32_t)x;
-    } else {
-      uint64_t x;
-      if (!d_colfer_u64(d, e0, n, i, (h & 0x80u) != 0, x)) return false;
-      switch (tag) {
-        case 0: e.term = x; break;
-        case 1: e.index = x; break;
-        case 3: e.key = x; break;
-        case 4: e.client_id = x; break;
-        case 5: e.series_id = x; break;
-        default: e.responded_to = x; break;
-      }
-    }
-    h = d[e0 + i++];
-  }
-  if (h == 7) {  // Cmd (raft_optimized.go:603-641)
-    uint64_t x = 0;
-    for (uint32_t s = 0;; s += 7) {
-      if (i >= n) return false;
-      const uint64_t b = d[e0 + i++];
-      x |= (b & 0x7f) << s;
-      if (b < 0x80) break;
-      if (s > 56) return false;
-    }
-    if (x > 16 * 1024 * 1024 || x >= n - i) return false;  // ColferSizeMax
-    e.cmd_off = i;
-    e.cmd_len = (uint32_t)x;
-    i += (uint32_t)x;
-    h = d[e0 + i++];
-  }
-  return h == 0x7fu && i == n;
-}
-
-__constant__ uint8_t c_empty_snapshot[24] = {
-    0x12, 0, 0x18, 0, 0x20, 0, 0x28, 0, 0x32, 2, 0x08, 0,
-    0x48, 0, 0x50, 0, 0x58, 0, 0x60, 0, 0x68, 0, 0x70, 0};
-
-// Message.Unmarshal (raft_optimized.go:659-983).  ents == nullptr: count
-// the entries only.  Returns ING_*; *big when a Cmd exceeds cmd_cap.
-__device__ inline uint32_t d_message(const uint8_t *msg, uint32_t n,
-                                     DecMsg &m, drb_entry *ents,
-                                     uint64_t base, uint32_t cmd_cap,
-                                     bool &big) {
-  Bytes d(msg);
-  m.shard = m.from = m.to = m.term = m.log_term = m.log_index = m.commit = 0;
-  m.hint = m.hint_high = 0;
-  m.type = m.reject = m.n_ent = 0;
-  uint32_t i = 0;
-  while (i < n) {
-    uint64_t wire, v;
-    if (!d_varint(d, n, i, wire)) return ING_BAD;
-    const uint64_t field = wire >> 3;
-    const uint32_t wt = (uint32_t)(wire & 7);
-    if (field == 0) return ING_BAD;
-    if ((field >= 1 && field <= 10) || field == 13) {
-      if (wt != 0 || !d_varint(d, n, i, v)) return ING_BAD;
-      switch (field) {
-        case 1: m.type = (uint32_t)v; break;
-        case 2: m.to = v; break;
-        case 3: m.from = v; break;
-        case 4: m.shard = v; break;
-        case 5: m.term = v; break;
-        case 6: m.log_term = v; break;
-        case 7: m.log_index = v; break;
-        case 8: m.commit = v; break;
-        case 9: m.reject = v != 0; break;
-        case 10: m.hint = v; break;
-        default: m.hint_high = v; break;
-      }
-    } else if (field == 11 || field == 12) {
-      uint64_t l;
-      if (wt != 2 || !d_varint(d, n, i, l) || l > n - i) return ING_BAD;
-      if (field == 11) {
-        drb_entry e;
-        if (!d_entry(d, i, (uint32_t)l, e)) return ING_BAD;
-        if (e.cmd_len > cmd_cap) big = true;
-        if (ents) {
-          e.cmd_off += base + i;  // the Cmd's offset in the stream
-          ents[m.n_ent] = e;
-        }
-        m.n_ent++;
-      } else {
-        bool empty = l == 24;
-        for (uint32_t k = 0; empty && k < 24; ++k)
-          empty = d[i + k] == c_empty_snapshot[k];
-        if (!empty) return ING_SNAPSHOT;  // InstallSnapshot: the CPU path
-      }
-      i += (uint32_t)l;
-    } else if (!d_skip(d, n, i, wire)) {
-      return ING_BAD;
-    }
-  }
-  return ING_OK;
-}
 
 // The payload CRC of a frame in 16 KB chunks, a workgroup per chunk:
 // thread t takes the 64 bytes that end 64 * (255 - t) bytes before the

@@ -157,15 +157,17 @@ long orc_entry_unmarshal(const uint8_t *d, size_t n, drb_entry *e,
     i++;
     if (x >= 0x80) {
       x &= 0x7f;
-      for (unsigned shift = 7;; shift += 7) {
+      /* no length limit (:400-415): Go's uint32 shifted by 32 or more is
+       * 0 (undefined in C, hence the test; shift stops growing there) */
+      for (unsigned shift = 7;; shift = shift < 32 ? shift + 7 : shift) {
         uint32_t b = d[i];
         i++;
         if (i >= n) return -1;
         if (b < 0x80) {
-          x |= b << shift;
+          if (shift < 32) x |= b << shift;
           break;
         }
-        x |= (b & 0x7f) << shift;
+        if (shift < 32) x |= (b & 0x7f) << shift;
       }
     }
     e->type = neg ? (~x + 1) : x;
@@ -182,15 +184,16 @@ long orc_entry_unmarshal(const uint8_t *d, size_t n, drb_entry *e,
     i++;
     if (x >= 0x80) {
       x &= 0x7f;
-      for (unsigned shift = 7;; shift += 7) {
+      /* no length limit (:613-625): Go's uint shifted by 64 or more is 0 */
+      for (unsigned shift = 7;; shift = shift < 64 ? shift + 7 : shift) {
         if (i >= n) return -1;
         uint64_t b = d[i];
         i++;
         if (b < 0x80) {
-          x |= b << shift;
+          if (shift < 64) x |= b << shift;
           break;
         }
-        x |= (b & 0x7f) << shift;
+        if (shift < 64) x |= (b & 0x7f) << shift;
       }
     }
     if (x > COLFER_SIZE_MAX) return -1;
@@ -277,8 +280,9 @@ static int skip_field(const uint8_t *d, size_t n, size_t *pi) {
     case 2: {
       uint64_t l;
       if (get_varint(d, n, pi, &l)) return -1;
+      if (l > n - *pi) return -1; /* (no sum that could wrap) */
       *pi += (size_t)l;
-      return *pi > n ? -1 : 0;
+      return 0;
     }
     case 5:
       *pi += 4;
@@ -482,15 +486,18 @@ long orc_message_unmarshal(const uint8_t *d, size_t n, drb_message *m,
                            drb_entry *ents, size_t ent_cap, size_t *n_ents,
                            uint8_t *pool, size_t pool_cap, size_t *pool_used) {
   size_t i = 0;
+  int snapshot = 0;
   memset(m, 0, sizeof(*m));
   m->entries_off = *n_ents;
   while (i < n) {
     size_t pre = i;
     uint64_t wire, v;
     if (get_varint(d, n, &i, &wire)) return -1;
-    uint64_t field = wire >> 3;
+    /* fieldNum := int32(wire >> 3), refused when <= 0 (:679-686) */
+    uint32_t f32 = (uint32_t)(wire >> 3);
     int wt = (int)(wire & 7);
-    if (wt == 4 || field == 0) return -1;
+    if (wt == 4 || f32 == 0 || f32 >= 0x80000000u) return -1;
+    uint32_t field = f32;
     if ((field >= 1 && field <= 10) || field == 13) {
       if (wt != 0) return -1;
       if (get_varint(d, n, &i, &v)) return -1;
@@ -511,7 +518,7 @@ long orc_message_unmarshal(const uint8_t *d, size_t n, drb_message *m,
       if (wt != 2) return -1;
       uint64_t l;
       if (get_varint(d, n, &i, &l)) return -1;
-      if (i + l > n) return -1;
+      if (l > n - i) return -1;
       if (field == 11) {
         if (*n_ents >= ent_cap) return -1;
         if (orc_entry_unmarshal(d + i, (size_t)l, &ents[*n_ents], pool,
@@ -519,9 +526,13 @@ long orc_message_unmarshal(const uint8_t *d, size_t n, drb_message *m,
           return -1;
         (*n_ents)++;
         m->n_entries++;
-      } else if (l != sizeof(EMPTY_SNAPSHOT) ||
-                 memcmp(d + i, EMPTY_SNAPSHOT, sizeof(EMPTY_SNAPSHOT))) {
-        return -2;
+      } else if (l != 0 && (l != sizeof(EMPTY_SNAPSHOT) ||
+                            memcmp(d + i, EMPTY_SNAPSHOT,
+                                   sizeof(EMPTY_SNAPSHOT)))) {
+        /* (no bytes: Snapshot.Unmarshal sets nothing, the empty one.)  The
+         * rest is still scanned: what follows malformed refuses the batch
+         * (:940-943, then the loop goes on) */
+        snapshot = 1;
       }
       i += (size_t)l;
     } else {
@@ -529,7 +540,7 @@ long orc_message_unmarshal(const uint8_t *d, size_t n, drb_message *m,
       if (skip_field(d, n, &i)) return -1;
     }
   }
-  return (long)i;
+  return snapshot ? -2 : (long)i;
 }
 
 /* ---- pb.MessageBatch (raftpb/messagebatch.go:23-70) ------------------- */
@@ -563,6 +574,7 @@ long orc_messagebatch_unmarshal(const uint8_t *d, size_t n, drb_message *ms,
                                 uint64_t *deployment_id, uint32_t *bin_ver,
                                 char *src, size_t src_cap, size_t *src_len) {
   size_t i = 0, cnt = 0, ne = 0, pu = 0;
+  int snapshot = 0;
   *deployment_id = 0;
   *bin_ver = 0;
   *src_len = 0;
@@ -577,12 +589,13 @@ long orc_messagebatch_unmarshal(const uint8_t *d, size_t n, drb_message *ms,
       if (wt != 2) return -1;
       uint64_t l;
       if (get_varint(d, n, &i, &l)) return -1;
-      if (i + l > n) return -1;
+      if (l > n - i) return -1;
       if (field == 1) {
         if (cnt >= cap) return -1;
         long rc = orc_message_unmarshal(d + i, (size_t)l, &ms[cnt], ents,
                                         ent_cap, &ne, pool, pool_cap, &pu);
-        if (rc < 0) return rc;
+        if (rc == -1) return -1;
+        if (rc == -2) snapshot = 1; /* (the rest can still refuse the batch) */
         cnt++;
       } else {
         if (l > src_cap) return -1;
@@ -602,7 +615,7 @@ long orc_messagebatch_unmarshal(const uint8_t *d, size_t n, drb_message *ms,
       if (skip_field(d, n, &i)) return -1;
     }
   }
-  return (long)cnt;
+  return snapshot ? -2 : (long)cnt;
 }
 
 /* ---- TCP framing (internal/transport/tcp.go:64-112,142-178) ----------- */

@@ -1038,6 +1038,24 @@ def message_marshal(m):
     return bytes(buf[:w])
 
 
+def message_unmarshal(data):
+    """Message.Unmarshal of one marshalled pb.Message -> (outcome, msg):
+    ("ok", msg() dict), ("bad", None) when Go refuses the bytes, or
+    ("snapshot", None) for a Snapshot that is not the empty one (-2)."""
+    cap = len(data) + 1  # an entry takes at least one byte
+    marr = (Message * 1)()
+    earr = (Entry * cap)()
+    pool = (C.c_uint8 * cap)()
+    ne, pu = C.c_size_t(0), C.c_size_t(0)
+    rc = lib().orc_message_unmarshal(_u8(data), len(data), marr, earr, cap,
+                                     C.byref(ne), pool, cap, C.byref(pu))
+    if rc == -2:
+        return "snapshot", None
+    if rc < 0:
+        return "bad", None
+    return "ok", _unpack_messages(marr, 1, earr, pool)[0]
+
+
 def messagebatch_marshal(msgs, deployment_id=0, source=b"",
                          bin_ver=TRANSPORT_BIN_VERSION):
     marr, n, earr, pool = build_messages(msgs)
