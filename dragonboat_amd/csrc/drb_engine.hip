@@ -19,6 +19,8 @@
 #include "../../include/drb_engine.h"
 #include "drb_layout.hpp"
 #include "drb_msg.hpp"
+#include "drb_place.hpp"
+#include "drb_rows.hpp"
 #include "drb_step.hpp"
 #include "drb_launch.hpp"
 #include "drb_hsa.hpp"
@@ -203,17 +205,6 @@ static int scatter(drb_engine *e, T *base, const std::vector<uint64_t> &idx,
   HIPCHK(hipStreamSynchronize(e->stream));
   return DRB_OK;
 }
-
-__host__ __device__ static inline uint4 mk4h(uint64_t a, uint64_t b) {
-  uint4 q;
-  q.x = (uint32_t)a;
-  q.y = (uint32_t)(a >> 32);
-  q.z = (uint32_t)b;
-  q.w = (uint32_t)(b >> 32);
-  return q;
-}
-static uint64_t lo64h(uint4 q) { return (uint64_t)q.x | ((uint64_t)q.y << 32); }
-static uint64_t hi64h(uint4 q) { return (uint64_t)q.z | ((uint64_t)q.w << 32); }
 
 __global__ void k_fill_u4(uint4 *p, uint64_t n, uint4 val) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -714,8 +705,8 @@ extern "C" int drb_import_replicas(drb_engine *e, uint64_t first_group,
       }
       for (uint32_t d = 0; d < DRB_RI_DEPTH; ++d) {
         iri.push_back(ri_ix(v, s, d, g));
-        dric.push_back(mk4h(c.ri[d].ctx_low, c.ri[d].ctx_high));
-        drii.push_back(mk4h(c.ri[d].index, c.ri[d].from));
+        dric.push_back(pack2(c.ri[d].ctx_low, c.ri[d].ctx_high));
+        drii.push_back(pack2(c.ri[d].index, c.ri[d].from));
         dricf.push_back(c.ri[d].confirmed);
       }
     }
@@ -798,10 +789,10 @@ extern "C" int drb_export_replicas(drb_engine *e, uint64_t first_group,
       }
       for (uint32_t q = 0; q < DRB_RI_DEPTH; ++q, ++d) {
         if (q >= o.ri_count) continue;
-        o.ri[q].ctx_low = lo64h(dric[d]);
-        o.ri[q].ctx_high = hi64h(dric[d]);
-        o.ri[q].index = lo64h(drii[d]);
-        o.ri[q].from = hi64h(drii[d]);
+        o.ri[q].ctx_low = q_lo(dric[d]);
+        o.ri[q].ctx_high = q_hi(dric[d]);
+        o.ri[q].index = q_lo(drii[d]);
+        o.ri[q].from = q_hi(drii[d]);
         o.ri[q].confirmed = dricf[d];
       }
     }
@@ -810,21 +801,33 @@ extern "C" int drb_export_replicas(drb_engine *e, uint64_t first_group,
 }
 
 // ---------------------------------------------------------------- log
+// (the row formats: drb_rows.hpp)
 static void entry_to_chunks(const View &v, const drb_entry &en,
                             const uint8_t *pool, uint4 *out /*3 + C16*/) {
-  out[0] = mk4h(en.term, en.key);
-  out[1] = mk4h(en.client_id, en.series_id);
-  out[2] = mk4h(en.responded_to, 0);
-  out[2].z = en.type;
-  out[2].w = en.cmd_len;
-  for (uint32_t c = 0; c < v.C16; ++c) {
-    uint8_t b[16] = {0};
-    for (uint32_t k = 0; k < 16; ++k) {
-      uint32_t o = c * 16 + k;
-      if (o < en.cmd_len) b[k] = pool[en.cmd_off + o];
-    }
-    memcpy(&out[ENT_META + c], b, 16);
+  ent_pack(en, out);
+  for (uint32_t c = 0; c < v.C16; ++c)
+    out[ENT_META + c] = cmd_chunk(pool + en.cmd_off, en.cmd_len, c);
+}
+
+// gathered entry rows of indexes lo, lo + 1, ... -> out[] and their Cmds,
+// back to back from the pool's start
+static int rows_to_entries(const View &v, const std::vector<uint4> &val,
+                           uint64_t lo, drb_entry *out, uint8_t *pool,
+                           size_t pool_cap) {
+  const size_t chunks = ENT_META + v.C16;
+  size_t used = 0;
+  for (size_t k = 0; k < val.size() / chunks; ++k) {
+    const uint4 *c = &val[k * chunks];
+    drb_entry &o = out[k];
+    ent_unpack(c, o);
+    o.index = lo + k;
+    o.cmd_off = used;
+    if (o.cmd_len > v.C16 * 16 || used + o.cmd_len > pool_cap)
+      return DRB_ERANGE;
+    memcpy(pool + used, &c[ENT_META], o.cmd_len);
+    used += o.cmd_len;
   }
+  return DRB_OK;
 }
 
 extern "C" int drb_import_log(drb_engine *e, uint64_t group, uint32_t slot,
@@ -881,25 +884,7 @@ extern "C" int drb_export_log(drb_engine *e, uint64_t group, uint32_t slot,
       idx.push_back(ring_ix(v, slot, i, c, group));
   std::vector<uint4> val;
   if (gather(e, v.ring, idx, val)) return DRB_EDEVICE;
-  size_t used = 0, k = 0;
-  for (uint64_t i = lo; i <= hi; ++i, ++k) {
-    const uint4 *c = &val[k * (ENT_META + v.C16)];
-    drb_entry &o = out[k];
-    o.term = lo64h(c[0]);
-    o.key = hi64h(c[0]);
-    o.client_id = lo64h(c[1]);
-    o.series_id = hi64h(c[1]);
-    o.responded_to = lo64h(c[2]);
-    o.type = c[2].z;
-    o.cmd_len = c[2].w;
-    o.index = i;
-    o.cmd_off = used;
-    if (o.cmd_len > v.C16 * 16 || used + o.cmd_len > pool_cap)
-      return DRB_ERANGE;
-    memcpy(pool + used, &c[ENT_META], o.cmd_len);
-    used += o.cmd_len;
-  }
-  return DRB_OK;
+  return rows_to_entries(v, val, lo, out, pool, pool_cap);
 }
 
 // ---------------------------------------------------------------- init
@@ -1023,23 +1008,17 @@ __global__ void k_init_steady(View v, uint64_t term, uint32_t leader,
   // resident window: R config-change entries (term 1) + the no-op (term)
   for (uint64_t i = 1; i <= L1; ++i) {
     bool cc = i <= R;
-    v.ring[ring_ix(v, s, i, 0, g)] = make_uint4(
-        (uint32_t)(cc ? 1 : term), (uint32_t)((cc ? 1 : term) >> 32), 0, 0);
-    v.ring[ring_ix(v, s, i, 1, g)] = make_uint4(0, 0, 0, 0);
     uint8_t b[32] = {0};
-    uint32_t len = cc ? cc_bytes((uint32_t)i, b) : 0;
-    v.ring[ring_ix(v, s, i, 2, g)] =
-        make_uint4(0, 0, cc ? DRB_ENTRY_CONFIG_CHANGE : DRB_ENTRY_APPLICATION,
-                   len);
-    for (uint32_t c = 0; c < v.C16; ++c) {
-      uint32_t w[4] = {0, 0, 0, 0};
-      for (uint32_t k = 0; k < 16; ++k) {
-        uint32_t o = c * 16 + k;
-        if (o < 32) w[k >> 2] |= (uint32_t)b[o] << (8 * (k & 3));
-      }
-      v.ring[ring_ix(v, s, i, ENT_META + c, g)] =
-          make_uint4(w[0], w[1], w[2], w[3]);
-    }
+    drb_entry en = {};
+    en.term = cc ? 1 : term;
+    en.type = cc ? DRB_ENTRY_CONFIG_CHANGE : DRB_ENTRY_APPLICATION;
+    en.cmd_len = cc ? cc_bytes((uint32_t)i, b) : 0;
+    uint4 meta[ENT_META];
+    ent_pack(en, meta);
+    for (uint32_t c = 0; c < ENT_META; ++c)
+      v.ring[ring_ix(v, s, i, c, g)] = meta[c];
+    for (uint32_t c = 0; c < v.C16; ++c)
+      v.ring[ring_ix(v, s, i, ENT_META + c, g)] = cmd_chunk(b, en.cmd_len, c);
   }
 }
 
@@ -1075,6 +1054,21 @@ extern "C" int drb_host_slot(drb_engine *e, uint32_t slot, int hosted) {
 }
 
 // ---------------------------------------------------------------- inputs
+// Proposal row j of lane g in batch `slot` (drb_rows.hpp): en with its Cmd
+// at cmd, or the capacity marker for a Cmd the row cannot hold or that is
+// not readable (outside the uploaded pool)
+DRB_DEV void stage_row(const View &v, uint32_t slot, uint32_t j, uint64_t g,
+                       const drb_entry &en, const uint8_t *cmd,
+                       bool readable) {
+  uint4 meta[PROP_META];
+  const bool held = prop_pack(v, en, cmd, readable, meta);
+  for (uint32_t c = 0; c < PROP_META; ++c)
+    v.props[prop_ix(v, slot, j, c, g)] = meta[c];
+  for (uint32_t c = 0; held && c < v.C16; ++c)
+    v.props[prop_ix(v, slot, j, PROP_META + c, g)] =
+        cmd_chunk(cmd, en.cmd_len, c);
+}
+
 // The entry queue as the host holds it (drb_entry rows + Cmd pool) is
 // uploaded as-is and laid out in the staged-proposal planes on the device:
 // one lane per group, entries j < counts[g] (the step reads no others).
@@ -1087,28 +1081,8 @@ __global__ void k_stage_props(View v, uint32_t slot, const uint32_t *counts,
   v.prop_count[(uint64_t)slot * v.G + g] = n;
   for (uint32_t j = 0; j < n; ++j) {
     const drb_entry en = ents[g * v.max_props + j];
-    const uint8_t *cmd = pool + en.cmd_off;
-    v.props[prop_ix(v, slot, j, 0, g)] = mk4h(en.key, en.client_id);
-    v.props[prop_ix(v, slot, j, 1, g)] = mk4h(en.series_id, en.responded_to);
-    if (en.cmd_len > v.C16 * 16 || en.cmd_off + en.cmd_len > pool_len) {
-      // a Cmd the staged planes cannot hold (or outside the pool): the
-      // leader's pre-pass sends the group to the CPU path (DRB_FB_CAPACITY)
-      v.props[prop_ix(v, slot, j, 2, g)] = make_uint4(en.type, ~0u, 1, 0);
-      continue;
-    }
-    const uint32_t b0 = en.cmd_len ? cmd[0] : 0u;
-    v.props[prop_ix(v, slot, j, 2, g)] = make_uint4(
-        en.type, en.cmd_len,
-        prop_fast(en.type, en.client_id, en.series_id, en.cmd_len, b0,
-                  v.snappy),
-        0);
-    for (uint32_t c = 0; c < v.C16; ++c) {
-      uint32_t w[4] = {0, 0, 0, 0};
-      for (uint32_t b = 0; b < 16 && c * 16 + b < en.cmd_len; ++b)
-        w[b >> 2] |= (uint32_t)cmd[c * 16 + b] << (8 * (b & 3));
-      v.props[prop_ix(v, slot, j, PROP_META + c, g)] =
-          make_uint4(w[0], w[1], w[2], w[3]);
-    }
+    stage_row(v, slot, j, g, en, pool + en.cmd_off,
+              en.cmd_off + en.cmd_len <= pool_len);
   }
 }
 
@@ -1187,26 +1161,13 @@ __global__ void k_stage_packed(View v, uint32_t slot, uint32_t type,
   const uint64_t sc = clients || !n ? 0ull : sess[g];
   for (uint32_t j = 0; j < n; ++j) {
     const uint64_t i = (uint64_t)ent0[g] + j;
-    const uint64_t key = keys[i], cid = clients ? clients[i] : sc;
-    const uint32_t len = lens[i];
     const uint64_t off = coff[i];
-    v.props[prop_ix(v, slot, j, 0, g)] = mk4h(key, cid);
-    v.props[prop_ix(v, slot, j, 1, g)] = make_uint4(0, 0, 0, 0);
-    if (len > v.C16 * 16 || off + len > pool_len) {  // CAPACITY (pre-pass)
-      v.props[prop_ix(v, slot, j, 2, g)] = make_uint4(type, ~0u, 1, 0);
-      continue;
-    }
-    const uint8_t *cmd = pool + off;
-    v.props[prop_ix(v, slot, j, 2, g)] = make_uint4(
-        type, len, prop_fast(type, cid, 0, len, len ? cmd[0] : 0u, v.snappy),
-        0);
-    for (uint32_t c = 0; c < v.C16; ++c) {
-      uint32_t w[4] = {0, 0, 0, 0};
-      for (uint32_t b = 0; b < 16 && c * 16 + b < len; ++b)
-        w[b >> 2] |= (uint32_t)cmd[c * 16 + b] << (8 * (b & 3));
-      v.props[prop_ix(v, slot, j, PROP_META + c, g)] =
-          make_uint4(w[0], w[1], w[2], w[3]);
-    }
+    drb_entry en = {};  // the NoOP session: no series, nothing responded to
+    en.key = keys[i];
+    en.client_id = clients ? clients[i] : sc;
+    en.type = type;
+    en.cmd_len = lens[i];
+    stage_row(v, slot, j, g, en, pool + off, off + en.cmd_len <= pool_len);
   }
 }
 
@@ -1546,7 +1507,7 @@ extern "C" int drb_stage_read_index(drb_engine *e, uint32_t slot,
   if (!e || slot >= e->cfg.ri_slots) return DRB_ERANGE;
   const uint64_t G = e->v.G;
   std::vector<uint4> host(G);
-  for (uint64_t g = 0; g < G; ++g) host[g] = mk4h(ctx_low[g], ctx_high[g]);
+  for (uint64_t g = 0; g < G; ++g) host[g] = pack2(ctx_low[g], ctx_high[g]);
   HIPCHK(hipMemcpyAsync(e->v.ri_in + (uint64_t)slot * G, host.data(),
                         G * sizeof(uint4), hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -1664,11 +1625,7 @@ namespace {
 struct InPlane {  // one (group, from, to) plane of this call
   uint64_t g;
   uint32_t from, to;
-  uint4 cur;      // header: tag | quiesce, info, sender term
-  uint64_t maxapp;
-  bool maxapp_valid;
-  bool remote;    // placement C4: the sender slot lives on another rank
-  uint64_t elo;   // remote: the first entry index of the entry rows
+  Plane p;  // its working state (drb_place.hpp)
 };
 }  // namespace
 
@@ -1743,8 +1700,7 @@ extern "C" int drb_ingest_ex(drb_engine *e, const drb_message *msgs, size_t n,
     auto it = pid.find(key);
     if (it == pid.end()) {
       it = pid.emplace(key, (uint32_t)planes.size()).first;
-      planes.push_back(
-          InPlane{g, from, to, make_uint4(0, 0, 0, 0), 0, false, false, 0});
+      planes.push_back(InPlane{g, from, to, Plane()});
     }
     mplane[i] = it->second;
     last_key = key;
@@ -1773,20 +1729,11 @@ extern "C" int drb_ingest_ex(drb_engine *e, const drb_message *msgs, size_t n,
        gather(e, v.maxapp_in, xidx[1], mx[1]) || gather(e, v.elo_in, lidx, lo)))
     return DRB_EDEVICE;
   for (int r = 0; r < 2; ++r)
-    for (size_t q = 0; q < pidx[r].size(); ++q) {
-      InPlane &pl = planes[pidx[r][q]];
-      uint4 cur = hdr[r][q];
-      if (!tag_is(cur.x, tag)) {  // nothing there yet this round
-        cur = pack2(0, 0);
-        cur.x = tag & MQ_TAG;
-      }
-      pl.cur = cur;
-      pl.maxapp = mx[r][q];
-      pl.maxapp_valid = mi_nrep(cur.y) > 0;
-      pl.remote = r == 1;
-      pl.elo = r && pl.maxapp_valid ? lo[q] : 0;
-    }
-  // 3. place every message in its plane, in order
+    for (size_t q = 0; q < pidx[r].size(); ++q)
+      planes[pidx[r][q]].p.open(hdr[r][q], mx[r][q], r ? lo[q] : 0, r == 1,
+                                tag);
+  // 3. place every message in its plane, in order, by the placement rule
+  // (drb_place.hpp)
   // [0] local arrays, [1] the inbound (remote) ones
   std::vector<uint64_t> ridx[2], eidx[2], tridx[2], trval[2], fwidx;
   std::vector<uint4> rval[2], eval[2], fwval;
@@ -1795,88 +1742,19 @@ extern "C" int drb_ingest_ex(drb_engine *e, const drb_message *msgs, size_t n,
     if (fate[i] != DRB_ING_PLACED) continue;
     const drb_message &m = msgs[i];
     InPlane &pl = planes[mplane[i]];
-    uint4 &cur = pl.cur;
     const uint64_t rk = pl.g * v.R + pl.to;
     if (flagged.count(rk)) {  // the receiver left the fast path in this call
       fate[i] = DRB_ING_DIVERTED;
       continue;
     }
-    // a GPU capacity: the receiver goes to the CPU path with this message
-    auto capacity = [&]() {
+    bool cmds_fit = true;
+    for (uint64_t x = 0; cmds_fit && x < m.n_entries; ++x)
+      cmds_fit = ents[m.entries_off + x].cmd_len <= v.C16 * 16;
+    if (!pl.p.fits(v, m.type, m.n_entries, m.log_index, cmds_fit)) {
+      // a GPU capacity: the receiver goes to the CPU path with this message
       flagged.emplace(rk, 1);
       fate[i] = DRB_ING_DIVERTED;
-    };
-    if (m.type == DRB_MSG_QUIESCE) {  // node-level: a header bit
-      cur.x |= MQ_QUIESCE;
       continue;
-    }
-    if (mi_count(cur.y) >= v.MB) {  // the plane's records
-      capacity();
-      continue;
-    }
-    const bool rep = m.type == DRB_MSG_REPLICATE;
-    const int r = pl.remote ? 1 : 0;
-    const uint32_t k = rep ? mi_nrep(cur.y)
-                           : rec_pos(false, mi_noth(cur.y), v.MB);
-    bool fit = true;
-    for (uint64_t x = 0; fit && x < m.n_entries; ++x)
-      fit = ents[m.entries_off + x].cmd_len <= v.C16 * 16;
-    if (m.type == DRB_MSG_PROPOSE) {
-      // handleFollowerPropose's message from another NodeHost: its entries
-      // go to the sender's forward rows, one Propose per plane and round
-      // (drb_config.forward_proposals)
-      fit = fit && v.fwd_props && !pl.remote && !(cur.y & MI_PROP) &&
-            m.n_entries <= v.max_props;
-    }
-    if (rep && pl.remote && m.n_entries) {
-      // entry rows [elo, elo + E), elo set by the round's first Replicate
-      // that carries entries (0: none yet; a commit-only Replicate needs no
-      // rows)
-      const uint64_t elo = pl.elo ? pl.elo : m.log_index + 1;
-      fit = fit && m.log_index + 1 >= elo &&
-            m.log_index + m.n_entries - elo < v.E;
-      if (fit) pl.elo = elo;
-    }
-    if (rep && m.n_entries > v.W) fit = false;  // (the window rows)
-    if (!fit) {
-      capacity();
-      continue;
-    }
-    if (m.type == DRB_MSG_PROPOSE) {
-      const uint32_t fw = fwd_ps(v, buf, pl.from);
-      for (uint64_t x = 0; x < m.n_entries; ++x) {
-        const drb_entry &en = ents[m.entries_off + x];
-        const uint8_t *cmd = pool + en.cmd_off;
-        std::vector<uint4> pc(PROP_META + v.C16, make_uint4(0, 0, 0, 0));
-        pc[0] = mk4h(en.key, en.client_id);
-        pc[1] = mk4h(en.series_id, en.responded_to);
-        pc[2] = make_uint4(en.type, en.cmd_len,
-                           prop_fast(en.type, en.client_id, en.series_id,
-                                     en.cmd_len, en.cmd_len ? cmd[0] : 0u,
-                                     v.snappy),
-                           0);
-        if (en.cmd_len) memcpy(&pc[PROP_META], cmd, en.cmd_len);
-        for (uint32_t c = 0; c < PROP_META + v.C16; ++c) {
-          fwidx.push_back(prop_ix(v, fw, (uint32_t)x, c, pl.g));
-          fwval.push_back(pc[c]);
-        }
-      }
-    }
-    if (rep && m.n_entries) {
-      // the entries travel in the sender's (unhosted) window slot, or in the
-      // plane's entry rows when the plane is remote
-      for (uint64_t x = 0; x < m.n_entries; ++x) {
-        drb_entry en = ents[m.entries_off + x];
-        en.index = m.log_index + 1 + x;
-        entry_to_chunks(v, en, pool, ch.data());
-        for (uint32_t c = 0; c < ENT_META + v.C16; ++c) {
-          eidx[r].push_back(
-              pl.remote ? embox_ix(v, buf, pl.from, pl.to,
-                                   (uint32_t)(en.index - pl.elo), c, pl.g)
-                        : ring_ix(v, pl.from, en.index, c, pl.g));
-          eval[r].push_back(ch[c]);
-        }
-      }
     }
     Msg mm;
     mm.type = m.type;
@@ -1888,42 +1766,46 @@ extern "C" int drb_ingest_ex(drb_engine *e, const drb_message *msgs, size_t n,
     mm.commit = m.commit;
     mm.hint = m.hint;
     mm.hint_high = m.hint_high;
-    uint4 c0, c1;
-    msg_encode(mm, pl.to, nullptr, c0, c1);
-    // the sender's term is stored once per (sender, receiver, round) in the
-    // header; a record whose term differs from it makes the receiver fall
-    // back (term gate, raft.go:1596-1609)
-    const bool zero = (c0.x & MF_TERM_ZERO) != 0;
-    bool other = false;
-    if (!zero) {
-      // a pre-vote record carries a term of its own (r.term + 1 or the
-      // granted one): it never seeds the header's term (drb_ingest_wire
-      // and the GPU's emit do the same)
-      const bool pv = is_prevote_type(m.type);
-      if (!pv && !(cur.y & MI_TERM)) {
-        cur.z = (uint32_t)m.term;
-        cur.w = (uint32_t)(m.term >> 32);
-      } else if (pv || q_hi(cur) != m.term) {
-        other = true;
-        c0.x |= MF_TERM_OTHER;
-        if (v.rterm) {  // elections: the raft launch reads it
-          tridx[r].push_back(rterm_ix(v, buf, pl.from, pl.to, k, pl.g));
-          trval[r].push_back(m.term);
+    PlaneRec rec;
+    if (!pl.p.add(v, mm, pl.to, rec)) continue;
+    const int r = pl.p.remote ? 1 : 0;
+    ridx[r].push_back(mbox_ix(v, buf, pl.from, pl.to, rec.k, 0, pl.g));
+    rval[r].push_back(rec.c0);
+    ridx[r].push_back(mbox_ix(v, buf, pl.from, pl.to, rec.k, 1, pl.g));
+    rval[r].push_back(rec.c1);
+    if (rec.own_term && v.rterm) {  // elections: the raft launch reads it
+      tridx[r].push_back(rterm_ix(v, buf, pl.from, pl.to, rec.k, pl.g));
+      trval[r].push_back(rec.term);
+    }
+    if (m.type == DRB_MSG_PROPOSE) {  // into the sender's forward rows
+      const uint32_t fw = fwd_ps(v, buf, pl.from);
+      for (uint64_t x = 0; x < m.n_entries; ++x) {
+        const drb_entry &en = ents[m.entries_off + x];
+        const uint8_t *cmd = pool + en.cmd_off;
+        uint4 meta[PROP_META];
+        prop_pack(v, en, cmd, true, meta);
+        for (uint32_t c = 0; c < PROP_META + v.C16; ++c) {
+          fwidx.push_back(prop_ix(v, fw, (uint32_t)x, c, pl.g));
+          fwval.push_back(c < PROP_META
+                              ? meta[c]
+                              : cmd_chunk(cmd, en.cmd_len, c - PROP_META));
         }
       }
     }
-    ridx[r].push_back(mbox_ix(v, buf, pl.from, pl.to, k, 0, pl.g));
-    rval[r].push_back(c0);
-    ridx[r].push_back(mbox_ix(v, buf, pl.from, pl.to, k, 1, pl.g));
-    rval[r].push_back(c1);
-    const uint32_t inf =
-        msg_info(m.type, zero, m.reject != 0, (uint32_t)m.n_entries) |
-        (other ? MI_TERM_OTHER : 0);
-    cur.y = (cur.y + (inf & MI_CNTS)) | (inf & ~MI_CNTS);
-    if (rep) {
-      const uint64_t ma = m.log_index + m.n_entries;
-      pl.maxapp = pl.maxapp_valid ? std::max(pl.maxapp, ma) : ma;
-      pl.maxapp_valid = true;
+    if (m.type == DRB_MSG_REPLICATE) {
+      // the entries travel in the sender's (unhosted) window slot, or in the
+      // plane's entry rows when the plane is remote
+      for (uint64_t x = 0; x < m.n_entries; ++x) {
+        const uint64_t index = m.log_index + 1 + x;
+        entry_to_chunks(v, ents[m.entries_off + x], pool, ch.data());
+        for (uint32_t c = 0; c < ENT_META + v.C16; ++c) {
+          eidx[r].push_back(
+              r ? embox_ix(v, buf, pl.from, pl.to,
+                           (uint32_t)(index - pl.p.elo), c, pl.g)
+                : ring_ix(v, pl.from, index, c, pl.g));
+          eval[r].push_back(ch[c]);
+        }
+      }
     }
   }
   for (size_t i = 0; i < n; ++i) {
@@ -1936,17 +1818,17 @@ extern "C" int drb_ingest_ex(drb_engine *e, const drb_message *msgs, size_t n,
   std::vector<uint64_t> xval[2], tidx, lval;
   for (int r = 0; r < 2; ++r)
     for (size_t p : pidx[r]) {
-      hval[r].push_back(planes[p].cur);
-      xval[r].push_back(planes[p].maxapp);
-      if (r) lval.push_back(planes[p].elo);
+      hval[r].push_back(planes[p].p.cur);
+      xval[r].push_back(planes[p].p.maxapp);
+      if (r) lval.push_back(planes[p].p.elo);
     }
   // tag bytes: one u64 word per (receiver, group), a byte per sender
   std::unordered_map<uint64_t, uint32_t> tw;
   std::vector<uint64_t> tmask;  // sender bytes to set per word
-  std::vector<uint64_t> tbyte;  // their values (tag_byte, drb_msg.hpp)
+  std::vector<uint64_t> tbyte;  // their values
   for (const InPlane &pl : planes) {
-    if (pl.remote) continue;  // (remote planes: the header's tag alone)
-    if (!(mi_count(pl.cur.y) || (pl.cur.x & MQ_QUIESCE))) continue;
+    uint8_t tb;
+    if (!pl.p.close(tb)) continue;  // (remote planes, planes left empty)
     const uint64_t w = ((uint64_t)buf * v.R + pl.to) * v.G + pl.g;
     auto it = tw.find(w);
     if (it == tw.end()) {
@@ -1956,7 +1838,7 @@ extern "C" int drb_ingest_ex(drb_engine *e, const drb_message *msgs, size_t n,
       tbyte.push_back(0);
     }
     tmask[it->second] |= 0xffull << (8 * pl.from);
-    tbyte[it->second] |= (uint64_t)tag_byte(tag, pl.cur.y) << (8 * pl.from);
+    tbyte[it->second] |= (uint64_t)tb << (8 * pl.from);
   }
   std::vector<uint64_t> tv;
   if ((v.rterm && scatter(e, v.rterm, tridx[0], trval[0])) ||
@@ -2790,25 +2672,7 @@ static int export_entry_rows(drb_engine *e, uint32_t buf, uint64_t g,
       idx.push_back(embox_ix(v, buf, from, to, (uint32_t)(i - elo), c, g));
   std::vector<uint4> val;
   if (gather(e, in_planes(e, from, to).embox, idx, val)) return DRB_EDEVICE;
-  size_t used = 0, k = 0;
-  for (uint64_t i = lo; i <= hi; ++i, ++k) {
-    const uint4 *c = &val[k * (ENT_META + v.C16)];
-    drb_entry &o = out[k];
-    o.term = lo64h(c[0]);
-    o.key = hi64h(c[0]);
-    o.client_id = lo64h(c[1]);
-    o.series_id = hi64h(c[1]);
-    o.responded_to = lo64h(c[2]);
-    o.type = c[2].z;
-    o.cmd_len = c[2].w;
-    o.index = i;
-    o.cmd_off = used;
-    if (o.cmd_len > v.C16 * 16 || used + o.cmd_len > pool_cap)
-      return DRB_ERANGE;
-    memcpy(pool + used, &c[ENT_META], o.cmd_len);
-    used += o.cmd_len;
-  }
-  return DRB_OK;
+  return rows_to_entries(v, val, lo, out, pool, pool_cap);
 }
 
 // the messages of one (sender, receiver) plane of mailbox buffer `buf`
@@ -2924,12 +2788,7 @@ static int export_pair(drb_engine *e, uint32_t buf, uint64_t g,
         const uint4 *q4 = &pv[j * chunks];
         drb_entry &en = ents[*ne + j];
         memset(&en, 0, sizeof(en));
-        en.key = lo64h(q4[0]);
-        en.client_id = hi64h(q4[0]);
-        en.series_id = lo64h(q4[1]);
-        en.responded_to = hi64h(q4[1]);
-        en.type = q4[2].x;
-        en.cmd_len = q4[2].y;
+        prop_unpack(q4, en);
         if (en.cmd_len > v.C16 * 16) return DRB_EINVAL;
         if (*np + en.cmd_len > pcap) return DRB_ERANGE;
         en.cmd_off = *np;
@@ -3019,9 +2878,9 @@ extern "C" int drb_export_ready_to_reads(drb_engine *e, uint64_t group,
   for (uint32_t k = 0; k < n && k < cap; ++k) {
     out[k].shard_id = v.first_shard_id + gid(v, slot, group);
     out[k].replica_id = slot + 1;
-    out[k].index = lo64h(val[2 * k]);
-    out[k].ctx_low = hi64h(val[2 * k]);
-    out[k].ctx_high = lo64h(val[2 * k + 1]);
+    out[k].index = q_lo(val[2 * k]);
+    out[k].ctx_low = q_hi(val[2 * k]);
+    out[k].ctx_high = q_lo(val[2 * k + 1]);
   }
   if (n_out) *n_out = n;
   return DRB_OK;
@@ -3638,7 +3497,7 @@ extern "C" int drb_kv_lookup(drb_engine *e, uint64_t group, uint32_t slot,
     bool used = (sl[0].z >> 31) & 1u;
     if (!used) return 1;
     uint32_t klen = sl[0].z & 0xffu, vlen = (sl[0].z >> 8) & 0xfffu;
-    if (klen == key_len && lo64h(sl[0]) == k8) {
+    if (klen == key_len && q_lo(sl[0]) == k8) {
       if (val_len) *val_len = vlen;
       if (vlen > val_cap) return DRB_ERANGE;
       return slot_value(e, sl, val, vlen);
@@ -3651,7 +3510,7 @@ extern "C" int drb_kv_lookup(drb_engine *e, uint64_t group, uint32_t slot,
     const uint4 *sl = &ch[q];
     if (!((sl[0].z >> 31) & 1u)) continue;
     uint32_t klen = sl[0].z & 0xffu, vlen = (sl[0].z >> 8) & 0xfffu;
-    if (klen == key_len && lo64h(sl[0]) == k8) {
+    if (klen == key_len && q_lo(sl[0]) == k8) {
       if (val_len) *val_len = vlen;
       if (vlen > val_cap) return DRB_ERANGE;
       return slot_value(e, sl, val, vlen);
@@ -3796,7 +3655,7 @@ extern "C" int drb_kv_export(drb_engine *e, uint64_t group, uint32_t slot,
     if (!((sl[0].z >> 31) & 1u)) continue;
     if (n < cap) {
       uint32_t klen = sl[0].z & 0xffu, vlen = (sl[0].z >> 8) & 0xfffu;
-      uint64_t k8 = lo64h(sl[0]);
+      uint64_t k8 = q_lo(sl[0]);
       for (uint32_t i = 0; i < 8; ++i) keys[n * 8 + i] = (uint8_t)(k8 >> (8 * i));
       key_lens[n] = klen;
       if (int rc = slot_value(e, sl, vals + n * v.kv_val_cap, vlen)) return rc;

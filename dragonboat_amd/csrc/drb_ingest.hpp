@@ -39,6 +39,9 @@
 // C++ shared with the host, also built under AddressSanitizer / UBSan by
 // tests/test_msgdecode_host.py
 #include "drb_msgdec.hpp"
+// the placement rule and the row formats (drb_ingest_ex's too)
+#include "drb_place.hpp"
+#include "drb_rows.hpp"
 
 namespace drb {
 
@@ -327,11 +330,9 @@ __global__ void k_ing_snaps(const uint32_t *mframe, const uint8_t *fstate,
     ing_cpu_push(cpu, cpu_n, cap, moff[i], mlen[i], DRB_ING_SNAPSHOT);
 }
 
-// one lane per plane (the head of a run of equal keys): MessageQueue.Add of
-// its messages in stream order (drb_engine.hip drb_ingest_ex, restated): a
-// message the plane cannot hold -- its records, a second Propose or one the
-// forward rows cannot take, a Replicate beyond a remote plane's entry rows
-// or the window, a Cmd over cmd_cap -- sends the receiver to the CPU path
+// one lane per plane (the head of a run of equal keys): its messages enter
+// the plane in stream order by the placement rule (drb_place.hpp).  A message
+// the plane cannot hold sends the receiver to the CPU path
 // (ing_flag_capacity) with it and the plane's later messages; a receiver
 // already off the fast path takes none (the CPU raft.Peer's)
 __global__ void k_ing_place(const View v, const uint8_t *s, const DecMsg *dm,
@@ -370,114 +371,22 @@ __global__ void k_ing_place(const View v, const uint8_t *s, const DecMsg *dm,
   // a receiver off the fast path: every message is the CPU path's
   bool div = (ft & (DRB_F_FALLBACK | DRB_F_ERROR)) != 0;
   const bool was_off = div;
-  uint4 cur = mmeta[mmeta_ix(v, buf, from, to, g)];
-  uint64_t maxapp = mmax[mmeta_ix(v, buf, from, to, g)];
-  if (!tag_is(cur.x, tag)) {  // nothing there yet this round
-    cur = make_uint4(tag & MQ_TAG, 0, 0, 0);
-  }
-  bool maxapp_valid = mi_nrep(cur.y) > 0;
-  // remote planes: the first entry index of the plane's entry rows (set by
-  // the round's first Replicate with entries placed here; 0: none yet)
-  uint64_t elo = maxapp_valid && rm ? v.elo_in[mmeta_ix(v, buf, from, to, g)]
-                                    : 0;
+  const uint64_t hx = mmeta_ix(v, buf, from, to, g);
+  Plane pl;
+  pl.open(mmeta[hx], mmax[hx], rm ? v.elo_in[hx] : 0, rm, tag);
   uint64_t acc = 0, ndiv = 0;
   for (uint64_t j = i0; j < i1; ++j) {
     const uint32_t mi = idx[j];
     const DecMsg m = dm[mi];
-    const bool rep = m.type == DRB_MSG_REPLICATE;
-    if (!div) {
-      if (m.type == DRB_MSG_QUIESCE) {  // node-level: a header bit
-        cur.x |= MQ_QUIESCE;
-        acc++;
-        continue;
-      }
-      bool fit = m.err == ING_OK && mi_count(cur.y) < v.MB;
-      if (fit && m.type == DRB_MSG_PROPOSE) {
-        // handleFollowerPropose's message from another NodeHost: its
-        // entries go to the sender's forward rows, one Propose per plane and
-        // round (drb_config.forward_proposals)
-        fit = v.fwd_props && !rm && !(cur.y & MI_PROP) &&
-              m.n_ent <= v.max_props;
-        for (uint32_t x = 0; fit && x < m.n_ent; ++x)
-          fit = ents[m.ent0 + x].cmd_len <= v.C16 * 16;
-      }
-      if (fit && rep && m.n_ent > v.W) fit = false;  // (the window rows)
-      if (fit && rep && rm && m.n_ent) {
-        // entry rows [elo, elo + E), elo set by the round's first
-        // Replicate that carries entries (a commit-only one needs none)
-        const uint64_t e0 = elo ? elo : m.log_index + 1;
-        fit = m.log_index + 1 >= e0 && m.log_index + m.n_ent - e0 < v.E;
-        if (fit) elo = e0;
-      }
-      div = !fit;
-    }
+    // (ING_BIG: a Cmd over cmd_cap, delivered undecoded)
+    div = div ||
+          !pl.fits(v, m.type, m.n_ent, m.log_index, m.err == ING_OK);
     if (div) {  // the CPU path's, in stream order after what was placed
       ing_cpu_push(cpu, cpu_n, cpu_cap, moff[mi], mlen[mi], DRB_ING_DIVERTED);
       ndiv++;
       continue;
     }
-    const uint32_t kk =
-        rep ? mi_nrep(cur.y) : rec_pos(false, mi_noth(cur.y), v.MB);
-    if (m.type == DRB_MSG_PROPOSE) {
-      const uint32_t fw = fwd_ps(v, buf, from);
-      for (uint32_t x = 0; x < m.n_ent; ++x) {
-        const drb_entry en = ents[m.ent0 + x];
-        const uint32_t b0 = en.cmd_len ? s[en.cmd_off] : 0u;
-        v.props[prop_ix(v, fw, x, 0, g)] = make_uint4(
-            (uint32_t)en.key, (uint32_t)(en.key >> 32), (uint32_t)en.client_id,
-            (uint32_t)(en.client_id >> 32));
-        v.props[prop_ix(v, fw, x, 1, g)] = make_uint4(
-            (uint32_t)en.series_id, (uint32_t)(en.series_id >> 32),
-            (uint32_t)en.responded_to, (uint32_t)(en.responded_to >> 32));
-        v.props[prop_ix(v, fw, x, 2, g)] = make_uint4(
-            en.type, en.cmd_len,
-            prop_fast(en.type, en.client_id, en.series_id, en.cmd_len, b0,
-                      v.snappy),
-            0);
-        for (uint32_t cc = 0; cc < v.C16; ++cc) {
-          uint32_t w[4] = {0, 0, 0, 0};
-          for (uint32_t b = 0; b < 16 && cc * 16 + b < en.cmd_len; ++b)
-            w[b >> 2] |= (uint32_t)s[en.cmd_off + cc * 16 + b] << (8 * (b & 3));
-          v.props[prop_ix(v, fw, x, PROP_META + cc, g)] =
-              make_uint4(w[0], w[1], w[2], w[3]);
-        }
-      }
-    }
-    if (rep && m.n_ent) {
-      // the entries travel in the sender's (unhosted) window slot, or in the
-      // plane's entry rows when the plane is remote
-      for (uint32_t x = 0; x < m.n_ent; ++x) {
-        const drb_entry en = ents[m.ent0 + x];
-        const uint64_t index = m.log_index + 1 + x;
-        uint4 ch[ENT_META];
-        ch[0] = make_uint4((uint32_t)en.term, (uint32_t)(en.term >> 32),
-                           (uint32_t)en.key, (uint32_t)(en.key >> 32));
-        ch[1] = make_uint4(
-            (uint32_t)en.client_id, (uint32_t)(en.client_id >> 32),
-            (uint32_t)en.series_id, (uint32_t)(en.series_id >> 32));
-        ch[2] = make_uint4((uint32_t)en.responded_to,
-                           (uint32_t)(en.responded_to >> 32), en.type,
-                           en.cmd_len);
-        for (uint32_t c = 0; c < ENT_META + v.C16; ++c) {
-          uint4 q;
-          if (c < ENT_META) {
-            q = ch[c];
-          } else {
-            const uint32_t cc = c - ENT_META;
-            uint32_t w[4] = {0, 0, 0, 0};
-            for (uint32_t b = 0; b < 16 && cc * 16 + b < en.cmd_len; ++b)
-              w[b >> 2] |= (uint32_t)s[en.cmd_off + cc * 16 + b]
-                           << (8 * (b & 3));
-            q = make_uint4(w[0], w[1], w[2], w[3]);
-          }
-          if (rm)
-            v.embox_in[embox_ix(v, buf, from, to, (uint32_t)(index - elo), c,
-                                g)] = q;
-          else
-            v.ring[ring_ix(v, from, index, c, g)] = q;
-        }
-      }
-    }
+    acc++;
     Msg mm;
     mm.type = m.type;
     mm.reject = m.reject ? 1 : 0;
@@ -488,45 +397,48 @@ __global__ void k_ing_place(const View v, const uint8_t *s, const DecMsg *dm,
     mm.commit = m.commit;
     mm.hint = m.hint;
     mm.hint_high = m.hint_high;
-    uint4 c0, c1;
-    msg_encode(mm, to, nullptr, c0, c1);
-    // the sender's term is stored once per (sender, receiver, round) in the
-    // header; a record whose term differs makes the receiver fall back
-    const bool zero = (c0.x & MF_TERM_ZERO) != 0;
-    bool other = false;
-    if (!zero) {
-      // a pre-vote record carries a term of its own (r.term + 1 or the
-      // granted one, not the sender's): it never seeds the header's term
-      // and always travels with its own (as the GPU's emit writes them)
-      const bool pv = is_prevote_type(m.type);
-      if (!pv && !(cur.y & MI_TERM)) {
-        cur.z = (uint32_t)m.term;
-        cur.w = (uint32_t)(m.term >> 32);
-      } else if (pv || q_hi(cur) != m.term) {
-        other = true;
-        c0.x |= MF_TERM_OTHER;
-        if (rterm) rterm[rterm_ix(v, buf, from, to, kk, g)] = m.term;
+    PlaneRec r;
+    if (!pl.add(v, mm, to, r)) continue;
+    mbox[mbox_ix(v, buf, from, to, r.k, 0, g)] = r.c0;
+    mbox[mbox_ix(v, buf, from, to, r.k, 1, g)] = r.c1;
+    if (r.own_term && rterm) rterm[rterm_ix(v, buf, from, to, r.k, g)] = r.term;
+    if (m.type != DRB_MSG_PROPOSE && m.type != DRB_MSG_REPLICATE) continue;
+    // a Propose's entries go to the sender's forward rows; a Replicate's
+    // travel in the sender's (unhosted) window slot, or in the plane's entry
+    // rows when the plane is remote
+    const bool prop = m.type == DRB_MSG_PROPOSE;
+    const uint32_t fw = fwd_ps(v, buf, from);
+    for (uint32_t x = 0; x < m.n_ent; ++x) {
+      const drb_entry en = ents[m.ent0 + x];
+      const uint8_t *cmd = s + en.cmd_off;
+      const uint64_t index = m.log_index + 1 + x;
+      static_assert(PROP_META == ENT_META, "one loop writes either row");
+      uint4 meta[ENT_META];
+      if (prop)
+        prop_pack(v, en, cmd, true, meta);
+      else
+        ent_pack(en, meta);
+      for (uint32_t c = 0; c < ENT_META + v.C16; ++c) {
+        const uint4 q =
+            c < ENT_META ? meta[c] : cmd_chunk(cmd, en.cmd_len, c - ENT_META);
+        if (prop)
+          v.props[prop_ix(v, fw, x, c, g)] = q;
+        else if (rm)
+          v.embox_in[embox_ix(v, buf, from, to, (uint32_t)(index - pl.elo), c,
+                              g)] = q;
+        else
+          v.ring[ring_ix(v, from, index, c, g)] = q;
       }
     }
-    mbox[mbox_ix(v, buf, from, to, kk, 0, g)] = c0;
-    mbox[mbox_ix(v, buf, from, to, kk, 1, g)] = c1;
-    const uint32_t inf = msg_info(m.type, zero, m.reject != 0, m.n_ent) |
-                         (other ? MI_TERM_OTHER : 0u);
-    cur.y = (cur.y + (inf & MI_CNTS)) | (inf & ~MI_CNTS);
-    if (rep) {
-      const uint64_t ma = m.log_index + m.n_ent;
-      maxapp = maxapp_valid ? umax64(maxapp, ma) : ma;
-      maxapp_valid = true;
-    }
-    acc++;
   }
   if (acc) {
-    mmeta[mmeta_ix(v, buf, from, to, g)] = cur;
-    mmax[mmeta_ix(v, buf, from, to, g)] = maxapp;
-    if (rm && maxapp_valid) v.elo_in[mmeta_ix(v, buf, from, to, g)] = elo;
-    if (!rm && (mi_count(cur.y) || (cur.x & MQ_QUIESCE)))  // its tag byte
+    mmeta[hx] = pl.cur;
+    mmax[hx] = pl.maxapp;
+    if (rm && pl.maxapp_valid) v.elo_in[hx] = pl.elo;
+    uint8_t tb;
+    if (pl.close(tb))  // its tag byte
       ((uint8_t *)&v.inbox_tag[((uint64_t)buf * v.R + to) * v.G + g])[from] =
-          tag_byte(tag, cur.y);
+          tb;
   }
   if (ndiv && !was_off) ing_flag_capacity(v, g, to, round);
   // (a lane per plane: the adds spread over the counter rows)
