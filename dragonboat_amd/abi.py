@@ -281,6 +281,30 @@ class RecoverStatus(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class TanMuxFile(C.Structure):
+    """drb_tan_mux_file: one file of the multiplexed log (slot, key)."""
+    _fields_ = [("slot", C.c_uint32), ("key", C.c_uint32),
+                ("log", C.c_uint32), ("pad", C.c_uint32),
+                ("off", C.c_uint64), ("len", C.c_uint64)]
+
+
+class RecoverMuxIn(C.Structure):
+    """drb_recover_mux_in."""
+    _fields_ = [("bytes", C.c_void_p), ("n_bytes", C.c_size_t),
+                ("files", C.POINTER(TanMuxFile)), ("n_files", C.c_size_t),
+                ("base_index", C.c_uint64), ("base_term", C.c_uint64),
+                ("seed", C.c_uint64)]
+
+
+class RecoverLogStatus(C.Structure):
+    """drb_recover_log_status: what drb_recover_tan_mux found of one log."""
+    _fields_ = [("status", C.c_uint32), ("log", C.c_uint32),
+                ("offset", C.c_uint64), ("records", C.c_uint64)]
+
+    def to_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class TanLog(C.Structure):
     """drb_tan_log: a multiplexed tan log's part of the last round."""
     _fields_ = [("start_offset", C.c_uint64), ("end_offset", C.c_uint64),

@@ -10,7 +10,8 @@ kinds for R = 3 and 5).  Each is its own translation unit
 objects build in parallel and only the ones whose sources changed rebuild;
 the engine's host code and auxiliary kernels are drb_engine.hip, the tan
 record kernels (drb_tan_inst.hip, twice) and the recovery kernels
-(drb_recover_inst.hip) units of their own.
+(drb_recover_inst.hip: drb_recover.hpp and, for the multiplexed tan logs,
+drb_recover_mux.hpp with its hipCUB scan and sort) units of their own.
 """
 import hashlib
 import os
@@ -36,9 +37,10 @@ STEP_DEPS = ["drb_step_inst.hip", "drb_step.hpp", "drb_lean.hpp",
              "drb_layout.hpp", "drb_msg.hpp", "drb_codec.hpp", "drb_ring.hpp",
              "drb_snappy.hpp"]
 # the recovery kernels' (drb_recover_inst.hip): the step kernel's headers
-# (apply_entry) and the tan read path
+# (apply_entry), the tan read path and the multiplexed logs' index
 RECOVER_DEPS = STEP_DEPS[1:] + ["drb_recover_inst.hip", "drb_recover.hpp",
-                                "drb_tanread.hpp"]
+                                "drb_tanread.hpp", "drb_recover_mux.hpp",
+                                "drb_tanmux.hpp"]
 # the tan record kernels' (drb_tan_inst.hip)
 TAN_DEPS = ["drb_tan_inst.hip", "drb_tan.hpp", "drb_launch.hpp",
             "drb_layout.hpp", "drb_codec.hpp", "drb_ring.hpp"]

@@ -4154,6 +4154,212 @@ extern "C" int drb_recover_tan(drb_engine *e, const drb_recover_in *in,
   return refresh_roles(e);
 }
 
+// ---- the multiplexed tan logs (drb_recover_mux.hpp)
+#include "drb_recover_mux.hpp"
+static_assert(sizeof(drb_recover_log_status) == sizeof(TmLogOut),
+              "drb_tanmux.hpp TmLogOut");
+
+extern "C" int drb_recover_tan_mux(drb_engine *e, const drb_recover_mux_in *in,
+                                   drb_recover_status *st,
+                                   drb_recover_log_status *lst) {
+  if (!e || !in || !st || !lst) return DRB_EINVAL;
+  if (e->round != 0 || !e->v.tan_mux || e->v.place_world > 1)
+    return DRB_EINVAL;
+  if ((in->n_bytes && !in->bytes) || (in->n_files && !in->files))
+    return DRB_EINVAL;
+  for (bool r : e->recovered)
+    if (r) return DRB_EINVAL;
+  const View &v = e->v;
+  const uint64_t NR = v.G * v.R;
+  const uint32_t NL = v.R * TM_KEYS;
+  const uint64_t kMax = 0x7fffffffull;  // (the scan and the sort count in int)
+  if (in->n_files > kMax || NR >= kMax) return DRB_ERANGE;
+  // the file table by log (a stable counting sort keeps the log order)
+  std::vector<uint32_t> first(NL + 1, 0);
+  uint64_t n_blocks = 0;
+  for (size_t i = 0; i < in->n_files; ++i) {
+    const drb_tan_mux_file &f = in->files[i];
+    if (f.slot >= v.R || f.key >= TM_KEYS || f.off > in->n_bytes ||
+        f.len > in->n_bytes - f.off)
+      return DRB_ERANGE;
+    first[f.slot * TM_KEYS + f.key + 1]++;
+    n_blocks += tm_blocks(f.len);
+  }
+  if (n_blocks > kMax) return DRB_ERANGE;
+  for (uint32_t L = 0; L < NL; ++L) first[L + 1] += first[L];
+  std::vector<TmFile> files(std::max<size_t>(in->n_files, 1));
+  std::vector<uint32_t> file_log(files.size(), 0);
+  std::vector<uint32_t> blk_file(std::max<uint64_t>(n_blocks, 1), 0);
+  {
+    std::vector<uint32_t> at(first.begin(), first.end() - 1);
+    for (size_t i = 0; i < in->n_files; ++i) {
+      const drb_tan_mux_file &f = in->files[i];
+      const uint32_t L = f.slot * TM_KEYS + f.key;
+      const uint32_t k = at[L]++;
+      if (k > first[L] && files[k - 1].log >= f.log) return DRB_EINVAL;
+      files[k] = TmFile{f.off, f.len, f.log, 0};
+      file_log[k] = L;
+    }
+    uint32_t b = 0;
+    for (size_t k = 0; k < in->n_files; ++k) {
+      files[k].blk0 = b;
+      for (uint64_t j = tm_blocks(files[k].len); j; --j) blk_file[b++] = k;
+    }
+  }
+  // (the call's temporaries: freed when it returns, behind run()'s wait)
+  DevBuf dbytes, dfiles, dfirst, dflog, dbfile, dsums, dentry, dcnt, dbase,
+      dlogs, dbad, dtmp, drecs, dkeys, dvals, dkeys2, dvals2, drep, dplans, dst,
+      dlst;
+  const size_t nb1 = blk_file.size();
+  const size_t scan_tb = recover_mux_scan_temp((uint32_t)nb1);
+  if (dbytes.reserve(in->n_bytes + 16) ||
+      dfiles.reserve(files.size() * sizeof(TmFile)) ||
+      dfirst.reserve(first.size() * sizeof(uint32_t)) ||
+      dflog.reserve(file_log.size() * sizeof(uint32_t)) ||
+      dbfile.reserve(nb1 * sizeof(uint32_t)) ||
+      dsums.reserve(nb1 * sizeof(TmBlock)) || dentry.reserve(nb1) ||
+      dcnt.reserve(nb1 * sizeof(uint32_t)) ||
+      dbase.reserve(nb1 * sizeof(uint32_t)) ||
+      dlogs.reserve(NL * sizeof(TmLogOut)) ||
+      dbad.reserve(NL * sizeof(unsigned long long)) ||
+      dtmp.reserve(std::max<size_t>(scan_tb, 16)) ||
+      drep.reserve(NR * sizeof(uint2)) || dplans.reserve(NR * sizeof(TrPlan)) ||
+      dst.reserve(NR * sizeof(drb_recover_status)) ||
+      dlst.reserve(NL * sizeof(drb_recover_log_status)))
+    return DRB_ENOMEM;
+  // DRB_RECOVER_TIMING=1 (tools/measure_recover.py --mux): device-event
+  // times of the upload and of each pass, one line on stderr
+  const char *tenv = getenv("DRB_RECOVER_TIMING");
+  const bool timing = tenv && tenv[0] == '1';
+  Event tev[8];
+  if (timing)
+    for (Event &ev : tev)
+      if (ev.create(hipEventDefault) != hipSuccess) return DRB_EDEVICE;
+  auto run = [&]() -> int {
+    if (timing) HIPCHK(hipEventRecord(tev[0], e->stream_h2d));
+    for (size_t o = 0; o < in->n_bytes; o += kRecoverPiece)
+      HIPCHK(hipMemcpyAsync(dbytes.as<uint8_t>() + o, in->bytes + o,
+                            std::min(kRecoverPiece, in->n_bytes - o),
+                            hipMemcpyHostToDevice, e->stream_h2d));
+    HIPCHK(hipMemcpyAsync(dfiles.p, files.data(), dfiles.cap,
+                          hipMemcpyHostToDevice, e->stream_h2d));
+    HIPCHK(hipMemcpyAsync(dfirst.p, first.data(), dfirst.cap,
+                          hipMemcpyHostToDevice, e->stream_h2d));
+    HIPCHK(hipMemcpyAsync(dflog.p, file_log.data(), dflog.cap,
+                          hipMemcpyHostToDevice, e->stream_h2d));
+    HIPCHK(hipMemcpyAsync(dbfile.p, blk_file.data(), dbfile.cap,
+                          hipMemcpyHostToDevice, e->stream_h2d));
+    if (timing) HIPCHK(hipEventRecord(tev[1], e->stream_h2d));
+    HIPCHK(hipEventRecord(e->ev_staged, e->stream_h2d));
+    HIPCHK(hipStreamWaitEvent(e->stream, e->ev_staged, 0));
+    MuxParams p;
+    memset(&p, 0, sizeof(p));
+    p.bytes = dbytes.as<uint8_t>();
+    p.files = dfiles.as<TmFile>();
+    p.log_first = dfirst.as<uint32_t>();
+    p.file_log = dflog.as<uint32_t>();
+    p.blk_file = dbfile.as<uint32_t>();
+    p.n_files = (uint32_t)in->n_files;
+    p.n_blocks = (uint32_t)n_blocks;
+    p.n_logs = NL;
+    p.sums = dsums.as<TmBlock>();
+    p.entry = dentry.as<uint8_t>();
+    p.cnt = dcnt.as<uint32_t>();
+    p.first = dbase.as<uint32_t>();
+    p.logs = dlogs.as<TmLogOut>();
+    p.log_bad = dbad.as<unsigned long long>();
+    p.rep = drep.as<uint2>();
+    p.base = RecBase{in->base_index, in->base_term, in->seed, e->ticks};
+    p.plans = dplans.as<TrPlan>();
+    p.st = dst.as<drb_recover_status>();
+    p.lst = dlst.as<drb_recover_log_status>();
+    if (timing) HIPCHK(hipEventRecord(tev[2], e->stream));
+    recover_mux_index(v, p, e->stream);
+    HIPCHK(hipGetLastError());
+    if (timing) HIPCHK(hipEventRecord(tev[3], e->stream));
+    // the record numbers, and how many there are (the table's size)
+    uint64_t n_recs = 0;
+    if (n_blocks) {
+      HIPCHK(recover_mux_scan(p, dtmp.p, scan_tb, e->stream));
+      uint32_t tail[2];
+      HIPCHK(hipMemcpyAsync(&tail[0], p.first + n_blocks - 1, 4,
+                            hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(&tail[1], p.cnt + n_blocks - 1, 4,
+                            hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipStreamSynchronize(e->stream));
+      n_recs = (uint64_t)tail[0] + tail[1];
+    }
+    // (nothing of the engine is written yet)
+    if (n_recs > kMax) return DRB_ERANGE;
+    p.n_recs = (uint32_t)n_recs;
+    size_t sort_tb = 0;
+    if (n_recs) {
+      sort_tb = recover_mux_sort_temp(p.n_recs, NR + 1);
+      if (drecs.reserve(n_recs * sizeof(TmRec)) ||
+          dkeys.reserve(n_recs * 4) || dvals.reserve(n_recs * 4) ||
+          dkeys2.reserve(n_recs * 4) || dvals2.reserve(n_recs * 4) ||
+          dtmp.reserve(std::max<size_t>(sort_tb, 16)))
+        return DRB_ENOMEM;
+      p.recs = drecs.as<TmRec>();
+      p.keys = dkeys.as<uint32_t>();
+      p.vals = dvals.as<uint32_t>();
+      p.skeys = dkeys2.as<uint32_t>();
+      p.svals = dvals2.as<uint32_t>();
+    }
+    if (timing) HIPCHK(hipEventRecord(tev[4], e->stream));
+    if (n_recs) {
+      recover_mux_records(v, p, e->stream);
+      HIPCHK(hipGetLastError());
+      HIPCHK(recover_mux_sort(p, dkeys2.as<uint32_t>(), dvals2.as<uint32_t>(),
+                              NR + 1, dtmp.p, sort_tb, e->stream));
+    }
+    if (timing) HIPCHK(hipEventRecord(tev[5], e->stream));
+    recover_mux_check(v, p, e->stream);
+    HIPCHK(hipGetLastError());
+    if (timing) HIPCHK(hipEventRecord(tev[6], e->stream));
+    recover_mux_place(v, p, e->stream);
+    HIPCHK(hipGetLastError());
+    if (timing) HIPCHK(hipEventRecord(tev[7], e->stream));
+    HIPCHK(hipMemcpyAsync(st, dst.p, NR * sizeof(drb_recover_status),
+                          hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(lst, dlst.p, NL * sizeof(drb_recover_log_status),
+                          hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (timing) {
+      float up = 0, pa = 0, sc = 0, pt = 0, p1 = 0, p2 = 0;
+      HIPCHK(hipEventElapsedTime(&up, tev[0], tev[1]));
+      HIPCHK(hipEventElapsedTime(&pa, tev[2], tev[3]));
+      HIPCHK(hipEventElapsedTime(&sc, tev[3], tev[4]));
+      HIPCHK(hipEventElapsedTime(&pt, tev[4], tev[5]));
+      HIPCHK(hipEventElapsedTime(&p1, tev[5], tev[6]));
+      HIPCHK(hipEventElapsedTime(&p2, tev[6], tev[7]));
+      size_t temp = 0;
+      for (const DevBuf *b : {&dfiles, &dfirst, &dflog, &dbfile, &dsums,
+                              &dentry, &dcnt, &dbase, &dlogs, &dbad, &dtmp,
+                              &drecs, &dkeys, &dvals, &dkeys2, &dvals2, &drep,
+                              &dplans, &dst, &dlst})
+        temp += b->cap;
+      fprintf(stderr,
+              "drb_recover_tan_mux: bytes=%zu blocks=%llu records=%llu "
+              "upload_ms=%.3f index_ms=%.3f scan_ms=%.3f partition_ms=%.3f "
+              "check_ms=%.3f place_ms=%.3f table_bytes=%zu temp_bytes=%zu\n",
+              in->n_bytes, (unsigned long long)n_blocks,
+              (unsigned long long)n_recs, up, pa, sc, pt, p1, p2,
+              (size_t)(drecs.cap + dkeys.cap + dvals.cap + dkeys2.cap +
+                       dvals2.cap),
+              temp + dbytes.cap);
+    }
+    return DRB_OK;
+  };
+  if (int rc = run()) {
+    (void)hipStreamSynchronize(e->stream_h2d);
+    (void)hipStreamSynchronize(e->stream);
+    return rc;
+  }
+  e->recovered.assign(e->cfg.num_groups, true);
+  return refresh_roles(e);
+}
+
 // ------------------------------------------------ batched round outputs
 // The round's ReadyToReads and served-read results of one replica slot
 // over a range of groups, compacted on the device: a per-lane record count,

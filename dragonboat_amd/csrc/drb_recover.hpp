@@ -56,6 +56,12 @@ struct RecParams {
   drb_recover_status *st;     // [n_groups * R], (g - first_group) * R + slot
 };
 
+// what a call hands every replica: the entry the logs continue from, the
+// seed of raft.rand, the engine's tick count
+struct RecBase {
+  uint64_t base_index, base_term, seed, qs_base;
+};
+
 // a workgroup is one wave: replicas' logs differ in length
 constexpr uint32_t REC_BLOCK = 64;
 
@@ -216,20 +222,17 @@ struct RingPlacer {
   }
 };
 
-__global__ __launch_bounds__(REC_BLOCK) void k_recover_place(View v,
-                                                             RecParams p) {
-  uint64_t q, g;
-  uint32_t slot;
-  if (!rec_lane(v, p, &q, &slot, &g)) return;
-  const TrPlan pl = p.plans[q];
-  if (pl.status != TRS_OK && pl.status != TRS_TAIL_CUT) return;
-  const uint32_t f0 = p.rep_first[q];
-  const RecFiles files{p.bytes, p.files + f0};
-  drb_recover_status &st = p.st[(g - p.first_group) * v.R + slot];
-  RingPlacer pc(v, slot, g, p.base_index, p.base_term, pl.term);
-  uint64_t applied = p.base_index;
-  const bool ok =
-      tr_replay(files, pl, rec_limits(v, p, slot, g), pc, &applied);
+// The end of pass 2 for replica (slot, g), behind the replay (`ok`: it ran
+// through; `applied`: its apply cursor): the KV count, then the restarted
+// node's state -- or, when the apply stopped, the fallback mark.  tan_state
+// is what the replica's tan_st becomes (save_tan).  Shared by the regular
+// and the multiplexed recovery (drb_recover_mux.hpp).
+__device__ inline void rec_place_finish(const View &v, const RecBase &p,
+                                        uint32_t slot, uint64_t g,
+                                        const TrPlan &pl, RingPlacer &pc,
+                                        bool ok, uint64_t applied,
+                                        drb_recover_status &st,
+                                        uint4 tan_state) {
   st.applied = applied;
   // KVTest.Count: the updates applied, and what the replica's record had
   // counted since the field was last written (word 15's delta, which the
@@ -327,10 +330,28 @@ __global__ __launch_bounds__(REC_BLOCK) void k_recover_place(View v,
     v.rem_state[rem_ix(v, slot, peer, g)] = DRB_REMOTE_RETRY;
     v.rem_active[rem_ix(v, slot, peer, g)] = 0;
   }
-  if (v.save_tan)  // the tan writer goes on behind the last kept record
-    v.tan_st[ix(v, slot, g)] =
-        make_uint4((uint32_t)pl.offset, (uint32_t)(pl.offset >> 32), st.log,
-                   pl.state_stored ? 1u /*TST_STATE*/ : 0u);
+  if (v.save_tan) v.tan_st[ix(v, slot, g)] = tan_state;
+}
+
+__global__ __launch_bounds__(REC_BLOCK) void k_recover_place(View v,
+                                                             RecParams p) {
+  uint64_t q, g;
+  uint32_t slot;
+  if (!rec_lane(v, p, &q, &slot, &g)) return;
+  const TrPlan pl = p.plans[q];
+  if (pl.status != TRS_OK && pl.status != TRS_TAIL_CUT) return;
+  const uint32_t f0 = p.rep_first[q];
+  const RecFiles files{p.bytes, p.files + f0};
+  drb_recover_status &st = p.st[(g - p.first_group) * v.R + slot];
+  RingPlacer pc(v, slot, g, p.base_index, p.base_term, pl.term);
+  uint64_t applied = p.base_index;
+  const bool ok =
+      tr_replay(files, pl, rec_limits(v, p, slot, g), pc, &applied);
+  // the tan writer goes on behind the last kept record
+  rec_place_finish(v, RecBase{p.base_index, p.base_term, p.seed, p.qs_base},
+                   slot, g, pl, pc, ok, applied, st,
+                   make_uint4((uint32_t)pl.offset, (uint32_t)(pl.offset >> 32),
+                              st.log, pl.state_stored ? 1u /*TST_STATE*/ : 0u));
 }
 
 }  // namespace drb

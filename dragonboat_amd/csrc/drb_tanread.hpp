@@ -602,6 +602,100 @@ struct TrReplay {
       : last(base), applied(base), high(base) {}
 };
 
+// One record of a replica in pass 1: the record whose chunks the caller has
+// walked and checked (payload of rlen bytes, the reader's state `before` in
+// front of it) is decoded and taken into the running state.  TRS_OK, or the
+// status that refuses the replica.  The same body for a replica's own log
+// files (tr_validate) and for its records in a multiplexed log
+// (drb_tanmux.hpp).
+template <class F>
+DRB_TR_FN uint32_t tr_validate_record(const F &f, const TanWalk &before,
+                                      uint64_t rlen, const TrLimits &lim,
+                                      TrReplay &rp, TrPlan &pl) {
+  TanCur<F> c(f, before, rlen);
+  TrUpdate u;
+  if (!tr_update_head(c, u)) return TRS_CORRUPT;
+  if (u.shard_id != lim.shard_id || u.replica_id != lim.replica_id)
+    return TRS_MISMATCH;
+  const uint64_t ck = u.has_state ? u.commit : rp.commit;
+  uint64_t first = 0, prev = 0;
+  for (uint32_t j = 0; j < u.n_entries; ++j) {
+    uint32_t n;
+    TrEntry e;
+    TrSkipCmd sink;
+    if (!tr_entry_len(c, &n) || !tr_entry(c, n, e, sink)) return TRS_CORRUPT;
+    if (j == 0) {
+      first = e.index;
+      // contiguity: an overwrite may start lower, never above last + 1
+      if (first == 0 || first > rp.last + 1) return TRS_GAP;
+      // an entry at or below a persisted commit is final
+      if (first > lim.base_index && first <= rp.applied) return TRS_CORRUPT;
+      // the pending span is applied from the window once this Update's
+      // first entry is placed: that entry must not take a pending one's
+      // place in the window
+      const uint64_t hi = ck < first - 1 ? ck : first - 1;
+      if (hi > rp.applied) {
+        const uint64_t high = first > rp.high ? first : rp.high;
+        if (high - rp.applied >= lim.W) return TRS_CAPACITY;
+        rp.applied = hi;
+      }
+    } else if (e.index != prev + 1) {
+      return TRS_GAP;
+    }
+    prev = e.index;
+    if (e.index > lim.base_index) {
+      if (!tr_fast(e, sink.first_byte, lim.snappy)) return TRS_ENTRY_TYPE;
+      if (e.cmd_len > lim.cmd_cap) return TRS_CAPACITY;
+      pl.entries++;
+      if (e.index <= ck && e.index > rp.applied) rp.applied = e.index;
+    }
+  }
+  bool snap;
+  if (!tr_update_tail(c, &snap)) return TRS_CORRUPT;
+  if (snap) return TRS_SNAPSHOT;
+  if (u.n_entries) rp.last = prev > lim.base_index ? prev : lim.base_index;
+  if (rp.last > rp.high) rp.high = rp.last;
+  if (u.has_state) {
+    rp.have_state = true;
+    rp.term = u.term;
+    rp.vote = u.vote;
+    rp.commit = u.commit;
+  }
+  pl.records++;
+  pl.state_stored = u.has_state;
+  return TRS_OK;
+}
+
+// The end of pass 1: what the kept records amount to (pl.status and the
+// final State), `cut` when the last log ended in an invalid record.
+DRB_TR_FN void tr_validate_finish(const TrReplay &rp, const TrLimits &lim,
+                                  bool cut, TrPlan &pl) {
+  if (!rp.have_state) {  // ErrNoSavedLog
+    pl.status = TRS_EMPTY;
+    return;
+  }
+  // the State's commit lies in the log above the base
+  if (rp.commit < lim.base_index) {
+    pl.status = TRS_GAP;
+    return;
+  }
+  if (rp.commit > rp.last) {
+    pl.status = TRS_CORRUPT;
+    return;
+  }
+  // the rest of (applied, commit] is applied from the window at the end
+  if (rp.commit > rp.applied && rp.high - rp.applied >= lim.W) {
+    pl.status = TRS_CAPACITY;
+    return;
+  }
+  pl.term = rp.term;
+  pl.vote = rp.vote;
+  pl.commit = rp.commit;
+  pl.last_index = rp.last;
+  pl.high_index = rp.high;
+  pl.status = cut ? TRS_TAIL_CUT : TRS_OK;
+}
+
 // Pass 1 for one replica: its files in log order (files[k] is file k, a
 // TanFile; an array or anything indexable).  Decides status, kept prefix and
 // final State without writing anything.
@@ -630,115 +724,62 @@ DRB_TR_FN TrPlan tr_validate(const FS &files, uint32_t n_files,
         pl.status = TRS_CORRUPT;
         return pl;
       }
-      TanCur<F> c(f, before, rlen);
-      TrUpdate u;
-      if (!tr_update_head(c, u)) {
-        pl.status = TRS_CORRUPT;
+      const uint32_t st = tr_validate_record(f, before, rlen, lim, rp, pl);
+      if (st != TRS_OK) {
+        pl.status = st;
         return pl;
       }
-      if (u.shard_id != lim.shard_id || u.replica_id != lim.replica_id) {
-        pl.status = TRS_MISMATCH;
-        return pl;
-      }
-      const uint64_t ck = u.has_state ? u.commit : rp.commit;
-      uint64_t first = 0, prev = 0;
-      for (uint32_t j = 0; j < u.n_entries; ++j) {
-        uint32_t n;
-        TrEntry e;
-        TrSkipCmd sink;
-        if (!tr_entry_len(c, &n) || !tr_entry(c, n, e, sink)) {
-          pl.status = TRS_CORRUPT;
-          return pl;
-        }
-        if (j == 0) {
-          first = e.index;
-          // contiguity: an overwrite may start lower, never above last + 1
-          if (first == 0 || first > rp.last + 1) {
-            pl.status = TRS_GAP;
-            return pl;
-          }
-          // an entry at or below a persisted commit is final
-          if (first > lim.base_index && first <= rp.applied) {
-            pl.status = TRS_CORRUPT;
-            return pl;
-          }
-          // the pending span is applied from the window once this Update's
-          // first entry is placed: that entry must not take a pending one's
-          // place in the window
-          const uint64_t hi = ck < first - 1 ? ck : first - 1;
-          if (hi > rp.applied) {
-            const uint64_t high = first > rp.high ? first : rp.high;
-            if (high - rp.applied >= lim.W) {
-              pl.status = TRS_CAPACITY;
-              return pl;
-            }
-            rp.applied = hi;
-          }
-        } else if (e.index != prev + 1) {
-          pl.status = TRS_GAP;
-          return pl;
-        }
-        prev = e.index;
-        if (e.index > lim.base_index) {
-          if (!tr_fast(e, sink.first_byte, lim.snappy)) {
-            pl.status = TRS_ENTRY_TYPE;
-            return pl;
-          }
-          if (e.cmd_len > lim.cmd_cap) {
-            pl.status = TRS_CAPACITY;
-            return pl;
-          }
-          pl.entries++;
-          if (e.index <= ck && e.index > rp.applied) rp.applied = e.index;
-        }
-      }
-      bool snap;
-      if (!tr_update_tail(c, &snap)) {
-        pl.status = TRS_CORRUPT;
-        return pl;
-      }
-      if (snap) {
-        pl.status = TRS_SNAPSHOT;
-        return pl;
-      }
-      if (u.n_entries) rp.last = prev > lim.base_index ? prev : lim.base_index;
-      if (rp.last > rp.high) rp.high = rp.last;
-      if (u.has_state) {
-        rp.have_state = true;
-        rp.term = u.term;
-        rp.vote = u.vote;
-        rp.commit = u.commit;
-      }
-      pl.records++;
-      pl.state_stored = u.has_state;
       pl.offset = tr_offset(w);
     }
   }
-  if (!rp.have_state) {  // ErrNoSavedLog
-    pl.status = TRS_EMPTY;
-    return pl;
-  }
-  // the State's commit lies in the log above the base
-  if (rp.commit < lim.base_index) {
-    pl.status = TRS_GAP;
-    return pl;
-  }
-  if (rp.commit > rp.last) {
-    pl.status = TRS_CORRUPT;
-    return pl;
-  }
-  // the rest of (applied, commit] is applied from the window at the end
-  if (rp.commit > rp.applied && rp.high - rp.applied >= lim.W) {
-    pl.status = TRS_CAPACITY;
-    return pl;
-  }
-  pl.term = rp.term;
-  pl.vote = rp.vote;
-  pl.commit = rp.commit;
-  pl.last_index = rp.last;
-  pl.high_index = rp.high;
-  pl.status = cut ? TRS_TAIL_CUT : TRS_OK;
+  tr_validate_finish(rp, lim, cut, pl);
   return pl;
+}
+
+// One kept record in pass 2 (no checksums; pass 1 accepted it): every entry
+// above the base handed to the placer, the committed ones applied.  false:
+// the placer stopped the replay.
+template <class F, class P>
+DRB_TR_FN bool tr_replay_record(const F &f, const TanWalk &before,
+                                uint64_t rlen, const TrLimits &lim,
+                                TrReplay &rp, P &placer, uint64_t *applied) {
+  TanCur<F> c(f, before, rlen);
+  TrUpdate u;
+  if (!tr_update_head(c, u)) return false;  // (pass 1 accepted it)
+  const uint64_t ck = u.has_state ? u.commit : rp.commit;
+  uint64_t prev = 0;
+  for (uint32_t j = 0; j < u.n_entries; ++j) {
+    uint32_t n;
+    TrEntry e;
+    if (!tr_entry_len(c, &n) || !tr_entry(c, n, e, placer)) return false;
+    if (e.index > lim.base_index) placer.place(e);
+    if (j == 0) {
+      const uint64_t hi = ck < e.index - 1 ? ck : e.index - 1;
+      while (rp.applied < hi) {
+        if (!placer.apply(rp.applied + 1)) return false;
+        *applied = ++rp.applied;
+      }
+    }
+    prev = e.index;
+    if (e.index > lim.base_index && e.index <= ck && e.index > rp.applied) {
+      if (!placer.apply(e.index)) return false;
+      *applied = rp.applied = e.index;
+    }
+  }
+  if (u.n_entries) rp.last = prev > lim.base_index ? prev : lim.base_index;
+  if (u.has_state) rp.commit = u.commit;
+  return true;
+}
+
+// The end of pass 2: the rest of (applied, commit] from the window
+template <class P>
+DRB_TR_FN bool tr_replay_finish(const TrPlan &pl, TrReplay &rp, P &placer,
+                                uint64_t *applied) {
+  while (rp.applied < pl.commit) {
+    if (!placer.apply(rp.applied + 1)) return false;
+    *applied = ++rp.applied;
+  }
+  return true;
 }
 
 // Pass 2 for one replica whose plan is TRS_OK or TRS_TAIL_CUT: the kept
@@ -766,39 +807,11 @@ DRB_TR_FN bool tr_replay(const FS &files, const TrPlan &pl,
       const TanWalk before = w;
       uint64_t rlen;
       if (tr_walk_record(f, w, false, &rlen) != TR_REC) break;
-      TanCur<F> c(f, before, rlen);
-      TrUpdate u;
-      if (!tr_update_head(c, u)) return false;  // (pass 1 accepted it)
-      const uint64_t ck = u.has_state ? u.commit : rp.commit;
-      uint64_t prev = 0;
-      for (uint32_t j = 0; j < u.n_entries; ++j) {
-        uint32_t n;
-        TrEntry e;
-        if (!tr_entry_len(c, &n) || !tr_entry(c, n, e, placer)) return false;
-        if (e.index > lim.base_index) placer.place(e);
-        if (j == 0) {
-          const uint64_t hi = ck < e.index - 1 ? ck : e.index - 1;
-          while (rp.applied < hi) {
-            if (!placer.apply(rp.applied + 1)) return false;
-            *applied = ++rp.applied;
-          }
-        }
-        prev = e.index;
-        if (e.index > lim.base_index && e.index <= ck &&
-            e.index > rp.applied) {
-          if (!placer.apply(e.index)) return false;
-          *applied = rp.applied = e.index;
-        }
-      }
-      if (u.n_entries) rp.last = prev > lim.base_index ? prev : lim.base_index;
-      if (u.has_state) rp.commit = u.commit;
+      if (!tr_replay_record(f, before, rlen, lim, rp, placer, applied))
+        return false;
     }
   }
-  while (rp.applied < pl.commit) {
-    if (!placer.apply(rp.applied + 1)) return false;
-    *applied = ++rp.applied;
-  }
-  return true;
+  return tr_replay_finish(pl, rp, placer, applied);
 }
 
 }  // namespace drb

@@ -156,6 +156,9 @@ SIGNATURES = {
                                C.POINTER(SZ), C.POINTER(C.c_int), PU64]),
     "drb_recover_tan": (C.c_int, [P, C.POINTER(abi.RecoverIn),
                                   C.POINTER(abi.RecoverStatus)]),
+    "drb_recover_tan_mux": (C.c_int, [P, C.POINTER(abi.RecoverMuxIn),
+                                      C.POINTER(abi.RecoverStatus),
+                                      C.POINTER(abi.RecoverLogStatus)]),
 }
 
 
@@ -735,6 +738,30 @@ class Engine:
             "drb_recover_tan")
         return {(first_group + gi, s): st[gi * self.R + s]
                 for gi in range(n_groups) for s in range(self.R)}
+
+    def recover_tan_mux(self, files, base_index, base_term, seed):
+        """drb_recover_tan_mux: every replica of a tan_multiplexed engine
+        restarts from its slot's shared logs.  files: {(slot, key): [(log
+        number, bytes), ...] in log order}.  Returns ({(group, slot):
+        abi.RecoverStatus}, {(slot, key): abi.RecoverLogStatus})."""
+        blob, table = bytearray(), []
+        for (s, key), logs in sorted(files.items()):
+            for lg, data in logs:
+                table.append(abi.TanMuxFile(s, key, lg, 0, len(blob),
+                                            len(data)))
+                blob += data
+        arr = (abi.TanMuxFile * max(1, len(table)))(*table)
+        buf = _u8(blob)
+        rin = abi.RecoverMuxIn(C.cast(buf, C.c_void_p), len(blob), arr,
+                               len(table), base_index, base_term, seed)
+        st = (abi.RecoverStatus * max(1, self.G * self.R))()
+        lst = (abi.RecoverLogStatus * (self.R * 16))()
+        _ck(lib().drb_recover_tan_mux(self.h, C.byref(rin), st, lst),
+            "drb_recover_tan_mux")
+        return ({(g, s): st[g * self.R + s]
+                 for g in range(self.G) for s in range(self.R)},
+                {(s, key): lst[s * 16 + key]
+                 for s in range(self.R) for key in range(16)})
 
     def export_save_records(self, g, slot):
         """save_batched: [(batch id, record value, crc32)] of one replica's

@@ -1536,6 +1536,75 @@ typedef struct drb_recover_status {
 int drb_recover_tan(drb_engine *e, const drb_recover_in *in,
                     drb_recover_status *st);
 
+/* drb_recover_tan_mux: the same restart for an engine with tan_multiplexed,
+ * from the 16 shared logs of every replica slot (CreateLogMultiplexedTan:
+ * log (slot, key) holds the records of the shards with ShardID % 16 == key;
+ * internal/tan/db.go, open.go:200-268, db_keeper.go:84-123 -- a shared db
+ * rebuilds one log for all its nodes).
+ *
+ * Needs drb_engine_round(e) == 0, save_tan with tan_multiplexed, replicas
+ * not placed over ranks, and no group recovered before: else DRB_EINVAL.
+ * The call covers every group of the engine (a log is shared by a sixteenth
+ * of them); afterwards every group counts as recovered, so a second call or
+ * a later drb_recover_tan is DRB_EINVAL.  `files` lists, per log (slot, key)
+ * in log order (increasing log numbers), where each file lies in `bytes`:
+ * slot >= R, key >= 16 or bytes outside `bytes` is DRB_ERANGE, files of a
+ * log out of order DRB_EINVAL, both before anything is uploaded.  n_files,
+ * the number of 32 KiB blocks and the number of records must each be below
+ * 2^31: else DRB_ERANGE, and nothing is done.
+ *
+ * The logs are indexed by their 32 KiB blocks in parallel, each file read
+ * as the record reader reads it, and the kept records handed to the
+ * replicas that own them (ShardID -> group, ReplicaID == slot + 1).
+ * lst[slot * 16 + key] reports each log:
+ *   DRB_REC_OK         every file read clean
+ *   DRB_REC_TAIL_CUT   an invalid record in the last file: the log ends
+ *                      there, to be truncated to `offset`; the records
+ *                      before it stand for every replica
+ *   DRB_REC_EMPTY      no file
+ *   DRB_REC_CORRUPT    a CRC mismatch anywhere, an invalid record in an
+ *                      earlier file, or a kept record whose ShardID /
+ *                      ReplicaID do not parse
+ *   DRB_REC_MISMATCH   a kept record of another ReplicaID, of a ShardID
+ *                      that is not a group of this engine, or of another key
+ * (chunk damage is found first; of the records, the first in log order
+ * decides).  Every replica of a log that is CORRUPT / MISMATCH / EMPTY gets
+ * the log's status, the first two with DRB_F_FALLBACK / DRB_FB_RECOVERY, and
+ * is otherwise untouched.  A replica of a log that stands (OK, TAIL_CUT) is
+ * recovered from the subsequence of the log's kept records that carry its
+ * ShardID, by drb_recover_tan's rules and with its statuses (DRB_REC_OK;
+ * _EMPTY: no State in any of its records; _GAP, _ENTRY_TYPE, _CAPACITY,
+ * _SNAPSHOT, _CORRUPT, _APPLY_STOPPED), and then holds byte for byte what
+ * drb_recover_tan leaves from the same records in a log of its own.  A
+ * refused replica does not refuse its log's other replicas.
+ *
+ * The writer of a log that stands continues at {log, offset} behind its last
+ * kept record; drb_recover_status.log / .offset of a replica report its
+ * log's (what drb_tan_get returns), and its stored State is non-empty when
+ * its own last kept record has one. */
+typedef struct drb_tan_mux_file {   /* one file of log (slot, key) */
+  uint32_t slot, key;               /* key = ShardID % 16 */
+  uint32_t log, pad;                /* log number */
+  uint64_t off, len;                /* in `bytes` */
+} drb_tan_mux_file;
+typedef struct drb_recover_mux_in {
+  const uint8_t *bytes;             /* host memory, pinned or not */
+  size_t n_bytes;
+  const drb_tan_mux_file *files;    /* per (slot, key) in log order */
+  size_t n_files;
+  uint64_t base_index, base_term, seed;  /* as drb_recover_in's */
+} drb_recover_mux_in;
+typedef struct drb_recover_log_status {  /* lst[slot * 16 + key] */
+  uint32_t status;    /* DRB_REC_OK, _TAIL_CUT, _EMPTY, _CORRUPT, _MISMATCH */
+  uint32_t log;       /* the log writer's log number */
+  uint64_t offset;    /* its offset: after the last kept record (truncate
+                       * here on TAIL_CUT) */
+  uint64_t records;   /* kept records of all its replicas */
+} drb_recover_log_status;
+int drb_recover_tan_mux(drb_engine *e, const drb_recover_mux_in *in,
+                        drb_recover_status *st,          /* [G * R], g * R + slot */
+                        drb_recover_log_status *lst);    /* [R * 16] */
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,8 +17,17 @@ The upload of the same bytes is the floor.  The CPU side of the comparison
 is the library's host reader (drb_tan_scan, one thread) over a sample of the
 logs, labelled host_scan: the oracle has no replay entry point to time.
 
+--mux adds the multiplexed format: the same workload written by a
+tan_multiplexed engine (one file per log: 16 logs a replica slot, each
+round's staged bytes of a log appended to its image), recovered with
+drb_recover_tan_mux after the regular recovery of the same shape, so that
+both are timed in one call.  Its JSON line (format "mux") has the upload,
+the block index (pass A and the composition), the scan with the one D2H of
+the record count, the partition (pass B and the sort), pass 1 and pass 2,
+the record-table bytes and the device bytes the call held.
+
   python tools/measure_recover.py [--groups N] [--entries K]
-                                  [--shapes c3,c5] [--repeats N]
+                                  [--shapes c3,c5] [--repeats N] [--mux]
 """
 import argparse
 import ctypes as C
@@ -139,8 +148,120 @@ def recover(cfg, G, start, total, blob, base):
         applied
 
 
+def _timed_call(fn):
+    """Runs fn with the library's stderr captured: (text, wall seconds)."""
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile() as tf:
+        os.dup2(tf.fileno(), 2)
+        try:
+            t0 = time.perf_counter()
+            fn()
+            wall = time.perf_counter() - t0
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+        tf.seek(0)
+        return tf.read().decode(), wall
+
+
+def write_mux_logs(G, shape, entries):
+    """(cfg, {(slot, key): bytes}) of a multiplexed engine's logs."""
+    cfg = dict(num_groups=G, num_replicas=3, window=max(64, entries * 2),
+               cmd_cap=shape["cmd_cap"], max_props=1, prop_slots=2,
+               ri_slots=1, mailbox=8, kv_slots=shape["kv_slots"],
+               kv_val_cap=shape["kv_val_cap"], save_cap=shape["save_cap"],
+               save_tan=1, tan_multiplexed=1, tan_max_log=1 << 40)
+    w = cfg["window"]
+    cfg["window"] = 1 << (w - 1).bit_length()
+    eng = Engine(**cfg)
+    eng.init_steady(term=2, leader_slot=0, seed=SEED)
+    logs = {(s, c): bytearray() for s in range(3) for c in range(16)}
+    for r in range(entries + 2):
+        k = 1 if r < entries else 0
+        if k:
+            eng.gen_kv_proposals(0, 1, 256, shape["val_len"], SEED, r)
+        out = eng.step(tick=(r % 2 == 0), prop_slot=0 if k else abi.DRB_NONE,
+                       encode_saves=True)
+        if out.fallbacks or out.errors:
+            raise RuntimeError("round %d: %s" % (r, out.to_dict()))
+        for key, img in logs.items():
+            lg, data = eng.export_tan_log(*key)
+            if lg["start_log"] or lg["end_log"] or \
+                    lg["start_offset"] != len(img):
+                raise RuntimeError("log %s: %s" % (key, lg))
+            img += data
+    eng.close()
+    return cfg, {k: v for k, v in logs.items() if v}
+
+
+MUX_TIMES = ("upload_ms", "index_ms", "scan_ms", "partition_ms", "check_ms",
+             "place_ms")
+
+
+def recover_mux(cfg, G, blob, table, base):
+    """One multiplexed recovery into a fresh engine."""
+    N = 3 * G
+    eng = Engine(**cfg)
+    rin = abi.RecoverMuxIn(blob.ctypes.data_as(C.c_void_p), blob.size, table,
+                           len(table), base, 2, SEED)
+    st = (abi.RecoverStatus * N)()
+    lst = (abi.RecoverLogStatus * 48)()
+    text, wall = _timed_call(lambda: en._ck(
+        en.lib().drb_recover_tan_mux(eng.h, C.byref(rin), st, lst),
+        "drb_recover_tan_mux"))
+    t = {}
+    for k in MUX_TIMES + ("records", "blocks", "table_bytes", "temp_bytes"):
+        m = re.search(r"%s=([\d.]+)" % k, text)
+        if not m:
+            raise RuntimeError("no timing line: %r" % text[-300:])
+        t[k] = float(m.group(1))
+    t["wall_ms"] = wall * 1e3
+    words = np.frombuffer(st, dtype=np.uint64).reshape(N, 9)
+    bad = int(((words[:, 0] & 0xffffffff) != abi.REC_OK).sum())
+    bad += sum(l.status != abi.REC_OK for l in lst)
+    ents = int(words[:, 3].sum())
+    applied = int((words[:, 8] - base).sum())
+    eng.close()
+    return t, bad, ents, applied
+
+
+def measure_mux(name, shape, G, entries, repeats):
+    cfg, logs = write_mux_logs(G, shape, entries)
+    table = (abi.TanMuxFile * len(logs))()
+    blob = np.empty(sum(len(v) for v in logs.values()), dtype=np.uint8)
+    off = 0
+    for i, ((s, c), img) in enumerate(sorted(logs.items())):
+        table[i] = abi.TanMuxFile(s, c, 0, 0, off, len(img))
+        blob[off:off + len(img)] = np.frombuffer(img, dtype=np.uint8)
+        off += len(img)
+    del logs
+    runs = []
+    for _ in range(repeats):
+        t, bad, ents, applied = recover_mux(cfg, G, blob, table, 4)
+        if bad:
+            raise RuntimeError("%s mux: %d not recovered" % (name, bad))
+        runs.append(t)
+    line = dict(shape=name, format="mux", groups=G, replicas=3, rounds=entries,
+                logs=len(table), log_bytes=int(blob.size), entries=ents,
+                applied=applied, records=int(runs[0]["records"]),
+                blocks=int(runs[0]["blocks"]),
+                table_bytes=int(runs[0]["table_bytes"]),
+                device_bytes=int(runs[0]["temp_bytes"]))
+    for k in MUX_TIMES + ("wall_ms",):
+        v = sorted(r[k] for r in runs)
+        line[k] = dict(runs=[round(r[k], 3) for r in runs],
+                       median=round(v[len(v) // 2], 3),
+                       spread=round(v[-1] - v[0], 3))
+    line["index_and_partition_over_upload"] = round(
+        (line["index_ms"]["median"] + line["scan_ms"]["median"] +
+         line["partition_ms"]["median"]) / line["upload_ms"]["median"], 3)
+    print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mux", action="store_true")
     ap.add_argument("--groups", type=int, default=262144)
     ap.add_argument("--entries", type=int, default=64)
     ap.add_argument("--shapes", default="c3,c5")
@@ -187,6 +308,9 @@ def main():
         line["applied_per_s"] = round(
             applied / (line["place_ms"]["median"] * 1e-3))
         print(json.dumps(line), flush=True)
+        if args.mux:
+            del blob
+            measure_mux(name, shape, G, args.entries, args.repeats)
 
 
 if __name__ == "__main__":
