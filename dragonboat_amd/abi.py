@@ -143,7 +143,9 @@ class Config(C.Structure):
                 ("nonvoting_slots", C.c_uint32),
                 ("witness_slots", C.c_uint32),
                 ("host_copies", C.c_uint32), ("no_lean", C.c_uint32),
-                ("entry_compression", C.c_uint32)]
+                ("entry_compression", C.c_uint32),
+                ("session_slots", C.c_uint32),
+                ("session_history", C.c_uint32)]
 
 
 class ReadResult(C.Structure):
@@ -162,6 +164,24 @@ class ApplyResult(C.Structure):
                 ("key", C.c_uint64), ("client_id", C.c_uint64),
                 ("series_id", C.c_uint64), ("value", C.c_uint64),
                 ("slot", C.c_uint32), ("ignored", C.c_uint32)]
+
+
+# drb_apply_result.ignored bits
+APPLY_IGNORED, APPLY_REJECTED = 1, 2
+
+# client.SeriesIDForRegister / SeriesIDForUnregister (client/session.pb.go)
+SERIES_REGISTER, SERIES_UNREGISTER = 2 ** 64 - 2, 2 ** 64 - 1
+
+
+class SessionRec(C.Structure):
+    """drb_session_rec: one client session of a replica."""
+    _fields_ = [("client_id", C.c_uint64), ("responded_up_to", C.c_uint64),
+                ("n_history", C.c_uint32), ("first_history", C.c_uint32)]
+
+
+class SessionResp(C.Structure):
+    """drb_session_resp: one cached response of a session."""
+    _fields_ = [("series_id", C.c_uint64), ("value", C.c_uint64)]
 
 
 # drb_worker_bufs value_meta codes (include/drb_engine.h)

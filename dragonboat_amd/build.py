@@ -35,7 +35,7 @@ LOCAL_KINDS, LOCAL_R = (9, 10, 11, 12), (3, 5)
 STEP_DEPS = ["drb_step_inst.hip", "drb_step.hpp", "drb_lean.hpp",
              "drb_launch.hpp",
              "drb_layout.hpp", "drb_msg.hpp", "drb_codec.hpp", "drb_ring.hpp",
-             "drb_snappy.hpp"]
+             "drb_snappy.hpp", "drb_session.hpp"]
 # the recovery kernels' (drb_recover_inst.hip): the step kernel's headers
 # (apply_entry), the tan read path and the multiplexed logs' index
 RECOVER_DEPS = STEP_DEPS[1:] + ["drb_recover_inst.hip", "drb_recover.hpp",

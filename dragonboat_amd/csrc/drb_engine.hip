@@ -274,6 +274,12 @@ static int validate_config(const drb_config *cfg) {
   if ((uint64_t)cfg->window * (128 + cfg->cmd_cap) > MAX_ENTRY_SIZE)
     return DRB_EINVAL;
   if (cfg->host_copies > 1 || cfg->entry_compression > 1) return DRB_EINVAL;
+  // client sessions: S = 0 with H = 0, or S in 1..16 with H in 1..8
+  if (cfg->session_slots > SESS_MAX_SLOTS ||
+      (cfg->session_slots ? cfg->session_history == 0 ||
+                                cfg->session_history > SESS_MAX_HISTORY
+                          : cfg->session_history != 0))
+    return DRB_EINVAL;
   // the ranks' groups cover total_groups (0: all of them)
   if (cfg->total_groups >
       cfg->num_groups * std::max<uint64_t>(cfg->place_world, 1))
@@ -394,6 +400,12 @@ extern "C" int drb_engine_create(const drb_config *cfg, drb_engine **out) {
   if (v.snappy) {  // the decoded payload's row per replica lane
     v.D16 = (16 + cfg->kv_val_cap + 15) / 16;
     rc |= dalloc(e, &v.snap, R * v.D16 * G);
+  }
+  v.sessions = cfg->session_slots;
+  v.sess_hist = cfg->session_history;
+  if (v.sessions) {  // the session tables and the apply's outcome ring
+    rc |= dalloc(e, &v.sess, R * v.sessions * (2ull + v.sess_hist) * G);
+    rc |= dalloc(e, &v.apply_out, R * v.W * G);
   }
   v.P = cfg->prop_slots;
   v.fwd_props = cfg->forward_proposals ? 1u : 0u;
@@ -1422,7 +1434,8 @@ __device__ static void gen_kv_lane(const View &v, uint32_t ps, uint32_t k,
     v.props[prop_ix(v, ps, j, 1, lane)] = mk4(0, 0);
     v.props[prop_ix(v, ps, j, 2, lane)] = make_uint4(
         DRB_ENTRY_ENCODED, clen,
-        prop_fast(DRB_ENTRY_ENCODED, cid, 0, clen, 0, v.snappy), 0);
+        prop_fast(DRB_ENTRY_ENCODED, cid, 0, clen, 0, v.snappy, v.sessions),
+        0);
   }
 }
 
@@ -2074,7 +2087,7 @@ static void launch_step(drb_engine *e, const RoundParams &p0,
   // the EXT instantiation only where its paths can run (drb_step.hpp)
   const bool ext =
       e->v.C16 > 4 || e->v.kv_ool || p0.encode_saves || e->v.quiesce ||
-      e->v.kv_ovf_cap || e->v.snappy;
+      e->v.kv_ovf_cap || e->v.snappy || e->v.sessions;
   pl.nrows = nl;
   pf.nrows = nf;
   // one-dimensional grids of the role's slot rows, row-major (block_pos);
@@ -2540,6 +2553,20 @@ __global__ __launch_bounds__(256) void k_apply_results(
       SnapRowsIn<uint4> in(v.ring + ring_ix(v, slot, idx, ENT_META, g), v.G);
       uint32_t next = 0;
       if (in.get(0) == 0x02) r.value = snappy_declared(in, clen, &next);
+    }
+    if (v.sessions) {
+      // the apply's own record of the entry (apply_done, drb_step.hpp):
+      // rejected and ignored session entries, a cached Result; a register
+      // or unregister's Value is the whole ClientID
+      const uint64_t o = v.apply_out[aout_ix(v, slot, idx, g)];
+      const uint32_t code = (uint32_t)(o >> 62);
+      r.ignored = code == SESS_CODE_IGNORED    ? DRB_APPLY_IGNORED
+                  : code == SESS_CODE_REJECTED ? DRB_APPLY_REJECTED
+                                               : 0u;
+      r.value = o & SESS_VALUE_MAX;
+      if (code == SESS_CODE_APPLIED && clen == 0 &&
+          r.series_id >= SESS_SERIES_REGISTER)
+        r.value = r.client_id;
     }
     r.slot = slot;
     out[pos + k] = r;
@@ -3665,6 +3692,70 @@ extern "C" int drb_kv_export(drb_engine *e, uint64_t group, uint32_t slot,
   }
   if (n_out) *n_out = n;
   return n > cap ? DRB_ERANGE : DRB_OK;
+}
+
+// ---------------------------------------------------------------- sessions
+// A replica's session table (drb_session.hpp) between the device, where its
+// chunks are G apart, and a flat host copy: one strided copy each way, the
+// table's own code on the host copy.
+static int sess_table_copy(drb_engine *e, uint64_t group, uint32_t slot,
+                           std::vector<SessQ> &tbl, bool to_device) {
+  const View &v = e->v;
+  const size_t chunks = (size_t)v.sessions * (2 + v.sess_hist);
+  tbl.resize(chunks);
+  uint4 *dev = v.sess + sess_ix(v, slot, group);
+  const size_t pitch = (size_t)v.G * sizeof(uint4);
+  if (to_device)
+    HIPCHK(hipMemcpy2DAsync(dev, pitch, tbl.data(), sizeof(SessQ),
+                            sizeof(SessQ), chunks, hipMemcpyHostToDevice,
+                            e->stream));
+  else
+    HIPCHK(hipMemcpy2DAsync(tbl.data(), sizeof(SessQ), dev, pitch,
+                            sizeof(SessQ), chunks, hipMemcpyDeviceToHost,
+                            e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return DRB_OK;
+}
+
+extern "C" int drb_sessions_export(drb_engine *e, uint64_t group,
+                                   uint32_t slot, drb_session_rec *recs,
+                                   size_t cap, drb_session_resp *hist,
+                                   size_t hist_cap, size_t *n_out,
+                                   size_t *n_hist_out) {
+  if (!e || !e->v.sessions || (cap && !recs) || (hist_cap && !hist))
+    return DRB_EINVAL;
+  if (group >= e->cfg.num_groups || slot >= e->cfg.num_replicas)
+    return DRB_ERANGE;
+  static_assert(sizeof(drb_session_rec) == sizeof(SessRec) &&
+                    sizeof(drb_session_resp) == sizeof(SessResp),
+                "drb_session.hpp restates the ABI's records");
+  std::vector<SessQ> tbl;
+  if (int rc = sess_table_copy(e, group, slot, tbl, false)) return rc;
+  const SessFlat<SessQ> t{tbl.data()};
+  size_t n = 0, nh = 0;
+  const bool fits =
+      sess_export(t, e->v.sessions, e->v.sess_hist, (SessRec *)recs, cap,
+                  (SessResp *)hist, hist_cap, &n, &nh);
+  if (n_out) *n_out = n;
+  if (n_hist_out) *n_hist_out = nh;
+  return fits ? DRB_OK : DRB_ERANGE;
+}
+
+extern "C" int drb_sessions_import(drb_engine *e, uint64_t group,
+                                   uint32_t slot, const drb_session_rec *recs,
+                                   size_t n, const drb_session_resp *hist,
+                                   size_t n_hist) {
+  if (!e || !e->v.sessions || (n && !recs) || (n_hist && !hist))
+    return DRB_EINVAL;
+  if (group >= e->cfg.num_groups || slot >= e->cfg.num_replicas)
+    return DRB_ERANGE;
+  std::vector<SessQ> tbl((size_t)e->v.sessions * (2 + e->v.sess_hist),
+                         SessQ{0, 0, 0, 0});
+  SessFlat<SessQ> t{tbl.data()};
+  if (!sess_import(t, e->v.sessions, e->v.sess_hist, (const SessRec *)recs, n,
+                   (const SessResp *)hist, n_hist))
+    return DRB_ERANGE;
+  return sess_table_copy(e, group, slot, tbl, true);
 }
 
 // ---------------------------------------------------------------- reads

@@ -298,18 +298,24 @@ constexpr int PROP_META = 3;
 // entry of the NoOP session (SeriesID 0; ClientID 0 only when empty), an
 // encoded Cmd carrying the v0 header byte 0x00 (no compression, no
 // session) or, with `snappy` (drb_config.entry_compression = 1), 0x02 (a
-// Snappy block, decoded by the apply: drb_snappy.hpp).  Computed when the
-// proposal is staged; anything else (config change, session management,
-// regular sessions, Snappy without the option) makes the leader fall back
-// before it appends (DRB_FB_ENTRY_TYPE).
+// Snappy block, decoded by the apply: drb_snappy.hpp).  With `sessions`
+// (drb_config.session_slots > 0) a client session's entries as well
+// (SeriesID != 0, drb_session.hpp): a register or unregister series with an
+// empty Cmd (client/session.pb.go:27-38), any other series with a Cmd that
+// passes what a NoOP-session entry's must.  Computed when the proposal is
+// staged; anything else (config change, sessions or Snappy without their
+// option) makes the leader fall back before it appends (DRB_FB_ENTRY_TYPE).
 __host__ __device__ inline uint32_t prop_fast(uint32_t type, uint64_t client_id,
                                               uint64_t series_id,
                                               uint32_t cmd_len,
                                               uint32_t first_byte,
-                                              uint32_t snappy) {
+                                              uint32_t snappy,
+                                              uint32_t sessions = 0) {
   if (type != 0 /*APPLICATION*/ && type != 2 /*ENCODED*/) return 0;
-  if (series_id != 0) return 0;
-  if (client_id == 0) return cmd_len == 0;
+  if (series_id != 0 && !sessions) return 0;
+  if (client_id == 0) return series_id == 0 && cmd_len == 0;
+  // SeriesIDForRegister / SeriesIDForUnregister (MaxUint64 - 1, MaxUint64)
+  if (series_id >= ~0ull - 1) return cmd_len == 0;
   if (type == 2 &&
       (cmd_len == 0 || !(first_byte == 0 || (snappy && first_byte == 2))))
     return 0;
@@ -479,6 +485,13 @@ struct View {
   // accepts; the row is reused entry after entry (null with the option off)
   uint32_t snappy, D16;
   uint4 *snap;
+  // drb_config.session_slots / session_history: the client session tables
+  // (drb_session.hpp), [R][S][2 + H][G] with the group innermost, and the
+  // apply's outcome per window entry, [R][W][G]: code << 62 | Result.Value
+  // (both null with the option off)
+  uint32_t sessions, sess_hist;
+  uint4 *sess;
+  uint64_t *apply_out;
 };
 
 // The escalation list of a row is split so that no one counter takes every
@@ -628,6 +641,15 @@ __host__ __device__ inline uint32_t fwd_ps(const View &v, uint32_t buf,
 __host__ __device__ inline uint64_t snap_ix(const View &v, uint32_t slot,
                                             uint32_t chunk, uint64_t g) {
   return ((uint64_t)slot * v.D16 + chunk) * v.G + g;
+}
+// chunk 0 of replica (slot, g)'s session table; its chunks are G apart
+__host__ __device__ inline uint64_t sess_ix(const View &v, uint32_t slot,
+                                            uint64_t g) {
+  return (uint64_t)slot * v.sessions * (2 + v.sess_hist) * v.G + g;
+}
+__host__ __device__ inline uint64_t aout_ix(const View &v, uint32_t slot,
+                                            uint64_t index, uint64_t g) {
+  return ((uint64_t)slot * v.W + (index & (v.W - 1))) * v.G + g;
 }
 __host__ __device__ inline uint64_t rres_ix(const View &v, uint32_t slot,
                                             uint32_t k, uint32_t j,

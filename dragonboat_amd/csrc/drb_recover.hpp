@@ -107,6 +107,7 @@ __device__ __forceinline__ TrLimits rec_limits(const View &v,
   lim.cmd_cap = v.C16 * 16;
   lim.W = v.W;
   lim.snappy = v.snappy;
+  lim.sessions = v.sessions;
   return lim;
 }
 

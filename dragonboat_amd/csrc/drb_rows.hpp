@@ -64,7 +64,7 @@ __host__ __device__ inline bool prop_pack(const View &v, const drb_entry &en,
   m[2] = held ? make_uint4(en.type, en.cmd_len,
                            prop_fast(en.type, en.client_id, en.series_id,
                                      en.cmd_len, en.cmd_len ? cmd[0] : 0u,
-                                     v.snappy),
+                                     v.snappy, v.sessions),
                            0)
               : make_uint4(en.type, ~0u, 1, 0);
   return held;

@@ -20,6 +20,7 @@
 #include "drb_layout.hpp"
 #include "drb_msg.hpp"
 #include "drb_ring.hpp"
+#include "drb_session.hpp"
 #include "drb_snappy.hpp"
 
 namespace drb {
@@ -1791,10 +1792,46 @@ static __device__ __noinline__ uint32_t snappy_to_row(const uint4 *cmd,
   return snappy_decode(in, clen, out, cap, &n) ? 0u : n;
 }
 
+// A session-managed entry against the replica's session table, whose chunks
+// are G apart (drb_session.hpp): the decision, without a store, and the
+// stores of a decided entry.  Calls, as the Snappy decoder is: the lookup's
+// sixteen client ids and the history's chunks stay out of the step
+// kernels' live ranges.  Inlined, the EXT follower (R = 3) spills 194 VGPRs
+// instead of 96; one callee that decides again at the commit, so that no
+// plan is live across the KV upsert, 196; the plan packed into three
+// registers, 108.
+static __device__ __noinline__ SessPlan sess_decide_rows(
+    uint4 *tbl, uint64_t G, uint32_t S, uint32_t H, uint64_t client,
+    uint64_t series, uint64_t responded_to, uint32_t clen) {
+  const SessRows<uint4> t{tbl, G};
+  return sess_decide(t, S, H, client, series, responded_to, clen);
+}
+static __device__ __noinline__ void sess_commit_rows(
+    uint4 *tbl, uint64_t G, uint32_t H, SessPlan sp, uint64_t client,
+    uint64_t series, uint64_t stamp, uint64_t value) {
+  SessRows<uint4> t{tbl, G};
+  sess_commit(t, H, sp, client, series, stamp, value);
+}
+
+// With sessions (EXT): an applied entry's outcome where drb_apply_results
+// reads it, and the session stores of an entry that has one (`sess`).
+DRB_DEV void apply_done(const Lane &L, uint64_t index, bool sess,
+                        const SessPlan &sp, uint64_t client, uint64_t series,
+                        uint32_t code, uint64_t value) {
+  const View &v = *L.v;
+  if (sess)
+    sess_commit_rows(v.sess + sess_ix(v, L.slot, L.g), v.G, v.sess_hist, sp,
+                     client, series, index + SESS_MAX_SLOTS, value);
+  v.apply_out[aout_ix(v, L.slot, index, L.g)] =
+      ((uint64_t)code << 62) | (value & SESS_VALUE_MAX);
+}
+
 // handleEntry (statemachine.go:935-969) -> update (1057-1103) ->
 // GetPayload (encoded.go:55-65) -> KVTest.Update (kvtest.go:145-162).
-// Returns: 0 noop applied, 1 KV updated, -1 not on the fast path, -2 the
-// KV table or the value pool is full.
+// Returns: 0 applied without a KV update (a no-op; with sessions, a
+// register, an unregister, a rejected, ignored or cached update), 1 KV
+// updated, -1 not on the fast path, -2 the KV table, the value pool or the
+// session table is full.
 // The PBKV header is parsed from the Cmd's first 64 bytes (registers); the
 // value is copied 16 B at a time straight from the window into the slot
 // (inline values) or the slot's value block (out-of-line, kv_val_cap >
@@ -1825,14 +1862,45 @@ DRB_DEV int apply_entry(const Lane &L, Rep<R> &r, uint64_t index) {
   uint64_t client_id = lo64(m1), series_id = hi64(m1);
   uint32_t type = m2.z, clen = m2.w;
   if (type == DRB_ENTRY_CONFIG_CHANGE) return -1;
+  // drb_config.session_slots (EXT): the entry's session decision, its
+  // stores held back until the entry has applied
+  bool sessions = false, sess = false;
+  SessPlan sp = SessPlan();
+  if constexpr (EXT) sessions = v.sessions != 0;
   if (client_id == 0) {  // not session managed
     if (clen != 0) return -1;  // reference panics
+    if constexpr (EXT)
+      if (sessions)
+        apply_done(L, index, false, sp, 0, 0, SESS_CODE_IGNORED, 0);
     r.sm_index = index;
     r.sm_term = term;
     r.applied_any = true;
     return 0;
   }
-  if (series_id != 0) return -1;  // sessions stay on the CPU path
+  if (series_id != 0) {
+    // without the option sessions stay on the CPU path
+    if (!sessions) return -1;
+    if constexpr (EXT) {
+      // what prop_fast refuses never reaches the table
+      if (type != DRB_ENTRY_APPLICATION && type != DRB_ENTRY_ENCODED)
+        return -1;
+      if (series_id >= SESS_SERIES_REGISTER && clen != 0) return -1;
+      sp = sess_decide_rows(v.sess + sess_ix(v, L.slot, L.g), v.G, v.sessions,
+                            v.sess_hist, client_id, series_id, lo64(m2), clen);
+      if (sp.outcome == SESS_FULL) return -2;
+      if (sp.outcome != SESS_UPDATE) {
+        // registerSession / unregisterSession (statemachine.go:1033-1045),
+        // or update's returns ahead of GetPayload (:1064-1080)
+        apply_done(L, index, true, sp, client_id, series_id,
+                   sess_code(sp.outcome), sp.value);
+        r.sm_index = index;
+        r.sm_term = term;
+        r.applied_any = true;
+        return 0;
+      }
+      sess = true;
+    }
+  }
   // the Cmd's first 64 bytes in registers: the PBKV header lies there
   if (EXT) {
     cmd.c0 = v.ring[ring_ix(v, L.slot, index, ENT_META, L.g)];
@@ -1959,6 +2027,12 @@ DRB_DEV int apply_entry(const Lane &L, Rep<R> &r, uint64_t index) {
       }
       sl[0] = make_uint4((uint32_t)key8, (uint32_t)(key8 >> 32),
                          (1u << 31) | (vlen << 8) | klen, w0);
+      // KVTest.Update's Result.Value is the payload's length (kvtest.go:
+      // 161): addResponse(series, result) (statemachine.go:1099-1101)
+      if constexpr (EXT)
+        if (sessions)
+          apply_done(L, index, sess, sp, client_id, series_id,
+                     SESS_CODE_APPLIED, plen);
       r.kv_added++;
       r.sm_index = index;
       r.sm_term = term;
@@ -1973,6 +2047,10 @@ DRB_DEV int apply_entry(const Lane &L, Rep<R> &r, uint64_t index) {
         put_value_long(v, L.slot, L.g, index, sl, hit, voff, vlen, pay)) {
       sl[0] = make_uint4((uint32_t)key8, (uint32_t)(key8 >> 32),
                          (1u << 31) | (vlen << 8) | klen, w0);
+      if constexpr (EXT)
+        if (sessions)
+          apply_done(L, index, sess, sp, client_id, series_id,
+                     SESS_CODE_APPLIED, plen);
       r.kv_added++;
       r.sm_index = index;
       r.sm_term = term;

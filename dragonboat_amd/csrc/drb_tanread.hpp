@@ -489,11 +489,13 @@ DRB_TR_FN bool tr_update_tail(C &c, bool *snapshot) {
 }
 
 // Whether the rsm fast path applies an entry: prop_fast (drb_layout.hpp)
-// restated for plain C++
-DRB_TR_FN bool tr_fast(const TrEntry &e, uint32_t first_byte, uint32_t snappy) {
+// restated for plain C++ (sessions: drb_config.session_slots > 0)
+DRB_TR_FN bool tr_fast(const TrEntry &e, uint32_t first_byte, uint32_t snappy,
+                       uint32_t sessions = 0) {
   if (e.type != 0 /*APPLICATION*/ && e.type != 2 /*ENCODED*/) return false;
-  if (e.series_id != 0) return false;
-  if (e.client_id == 0) return e.cmd_len == 0;
+  if (e.series_id != 0 && !sessions) return false;
+  if (e.client_id == 0) return e.series_id == 0 && e.cmd_len == 0;
+  if (e.series_id >= ~0ull - 1) return e.cmd_len == 0;
   if (e.type == 2 &&
       (e.cmd_len == 0 || !(first_byte == 0 || (snappy && first_byte == 2))))
     return false;
@@ -562,6 +564,7 @@ struct TrLimits {
   uint64_t base_index;  // entries at or below it are skipped
   uint32_t cmd_cap, W;  // Cmd bytes and entries the window holds
   uint32_t snappy;      // drb_config.entry_compression
+  uint32_t sessions = 0;  // drb_config.session_slots > 0
 };
 
 // what pass 1 decides about a replica; pass 2 replays `files` files, the
@@ -644,7 +647,8 @@ DRB_TR_FN uint32_t tr_validate_record(const F &f, const TanWalk &before,
     }
     prev = e.index;
     if (e.index > lim.base_index) {
-      if (!tr_fast(e, sink.first_byte, lim.snappy)) return TRS_ENTRY_TYPE;
+      if (!tr_fast(e, sink.first_byte, lim.snappy, lim.sessions))
+        return TRS_ENTRY_TYPE;
       if (e.cmd_len > lim.cmd_cap) return TRS_CAPACITY;
       pl.entries++;
       if (e.index <= ck && e.index > rp.applied) rp.applied = e.index;

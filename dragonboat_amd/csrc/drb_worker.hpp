@@ -419,6 +419,9 @@ extern "C" int drb_worker_export_part(drb_engine *e, uint32_t slot,
   if (!e || !b || slot >= e->v.R || !n_parts || part >= n_parts)
     return DRB_EINVAL;
   const View &v = e->v;
+  // its one-word records cannot say rejected or cached: with sessions the
+  // applied entries go through drb_apply_results
+  if (v.sessions) return DRB_EINVAL;
   // the partition's lanes: ShardID % n_parts == part (FixedPartitioner,
   // internal/server/partition.go:38), i.e. every n_parts-th lane from g0
   // (co-resident placement: lane g is ShardID first_shard_id + g)

@@ -109,6 +109,11 @@ SIGNATURES = {
     "drb_kv_export": (C.c_int, [P, U64, U32, PU8, PU32, PU8, PU32, SZ,
                                 C.POINTER(SZ)]),
     "drb_kv_import": (C.c_int, [P, U64, U32, PU8, PU32, PU8, PU32, SZ, SZ]),
+    "drb_sessions_export": (C.c_int, [P, U64, U32, C.POINTER(abi.SessionRec),
+                                      SZ, C.POINTER(abi.SessionResp), SZ,
+                                      C.POINTER(SZ), C.POINTER(SZ)]),
+    "drb_sessions_import": (C.c_int, [P, U64, U32, C.POINTER(abi.SessionRec),
+                                      SZ, C.POINTER(abi.SessionResp), SZ]),
     "drb_crc32_ieee_batch": (C.c_int, [P, PU8, SZ, PU64, PU32, SZ, PU32]),
     "drb_export_saved": (C.c_int, [P, U64, U32, PU8, SZ, PU32, PU32]),
     "drb_saved_buffers": (C.c_int, [P, C.POINTER(P), C.POINTER(PU32),
@@ -238,7 +243,8 @@ DEFAULTS = dict(num_groups=1, first_shard_id=1, num_replicas=3, window=32,
                 tan_multiplexed=0, pre_vote=0, max_reads_per_ctx=0,
                 kv_overflow_buckets=0, forward_proposals=0,
                 nonvoting_slots=0, witness_slots=0, host_copies=0,
-                no_lean=0, entry_compression=0)
+                no_lean=0, entry_compression=0, session_slots=0,
+                session_history=0)
 
 
 class Engine:
@@ -263,7 +269,8 @@ class Engine:
                    cfg["max_reads_per_ctx"], cfg["kv_overflow_buckets"],
                    cfg["forward_proposals"], cfg["nonvoting_slots"],
                    cfg["witness_slots"], cfg["host_copies"],
-                   cfg["no_lean"], cfg["entry_compression"])
+                   cfg["no_lean"], cfg["entry_compression"],
+                   cfg["session_slots"], cfg["session_history"])
         h = P()
         _ck(lib().drb_engine_create(C.byref(c), C.byref(h)),
             "drb_engine_create")
@@ -668,6 +675,38 @@ class Engine:
             kl[i], vl[i] = len(k), len(x)
         _ck(lib().drb_kv_import(self.h, g, slot, keys, kl, vals, vl, stride,
                                 n), "drb_kv_import")
+
+    def sessions_export(self, g, slot):
+        """Replica (g, slot)'s client sessions, least recently used first
+        (drb_sessions_export): [(client_id, responded_up_to, {series:
+        value})]."""
+        cap = max(1, self.cfg["session_slots"])
+        hcap = max(1, cap * self.cfg["session_history"])
+        recs, hist = (abi.SessionRec * cap)(), (abi.SessionResp * hcap)()
+        n, nh = SZ(), SZ()
+        _ck(lib().drb_sessions_export(self.h, g, slot, recs, cap, hist, hcap,
+                                      C.byref(n), C.byref(nh)),
+            "drb_sessions_export")
+        return [(r.client_id, r.responded_up_to,
+                 {hist[r.first_history + i].series_id:
+                  hist[r.first_history + i].value
+                  for i in range(r.n_history)}) for r in recs[:n.value]]
+
+    def sessions_import(self, g, slot, sessions):
+        """Replaces replica (g, slot)'s session table with `sessions` in
+        sessions_export's form and order (drb_sessions_import)."""
+        n = len(sessions)
+        recs = (abi.SessionRec * max(1, n))()
+        nh = sum(len(h) for _, _, h in sessions)
+        hist = (abi.SessionResp * max(1, nh))()
+        at = 0
+        for i, (c, upto, h) in enumerate(sessions):
+            recs[i] = abi.SessionRec(c, upto, len(h), at)
+            for s, v in h.items():
+                hist[at] = abi.SessionResp(s, v)
+                at += 1
+        _ck(lib().drb_sessions_import(self.h, g, slot, recs, n, hist, at),
+            "drb_sessions_import")
 
     def export_saved(self, g, slot):
         """(EntryBatch bytes, crc32) of one replica's last EntriesToSave."""

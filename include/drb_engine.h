@@ -446,6 +446,38 @@ typedef struct drb_config {
    * untouched.  0: such entries are not on the fast path (the leader falls
    * back before appending, DRB_FB_ENTRY_TYPE).  Other values: DRB_EINVAL. */
   uint32_t entry_compression;
+  /* Client sessions (dragonboat's default, at-most-once client mode:
+   * SyncGetSession, then proposals with SeriesID != 0).  session_slots (S):
+   * the sessions resident per replica, 1..16, 0 = off; session_history (H):
+   * the cached responses per session, 1..8 with S > 0, 0 with S = 0;
+   * anything else is DRB_EINVAL.  With S > 0 the apply runs the rsm session
+   * code on the device (dragonboat_amd/csrc/drb_session.hpp):
+   *   entry classes (raftpb/raft.go:87-128): SeriesID MaxUint64 - 1 / MaxUint64
+   *     with an empty Cmd registers / unregisters the ClientID
+   *     (client/session.pb.go:27-38); any other SeriesID != 0 is an update
+   *   handleEntry (internal/rsm/statemachine.go:935-969): RegisterClientID /
+   *     UnregisterClientID (sessionmanager.go:54-83) answer Result{Value:
+   *     ClientID}, or the empty Result -- rejected -- for a known / an unknown
+   *     client; update (:1057-1103) rejects an unregistered client, else runs
+   *     Session.clearTo(RespondedTo) (session.go:88-103), ignores a series
+   *     already responded to, answers a series in the history with the cached
+   *     Result and leaves the state machine alone, and otherwise updates the
+   *     KV and records the response
+   *   every lookup hit and every add makes the session the most recently used
+   *     (lrusession.go); drb_sessions_export walks least recently used first
+   *     (lrusession.go:93-120)
+   * The tables are R x G x S x (2 + H) x 16 bytes and the per-entry outcomes
+   * R x G x window x 8 bytes, both counted by drb_engine_device_bytes.  There
+   * is no eviction (LRUMaxSessionCount = 4096, settings/hard.go:124): a
+   * register with no free slot, or an update with no free history slot after
+   * its own clearTo, stops the replica's apply at the entry as a full KV
+   * does (DRB_F_APPLY_STOPPED, DRB_FB_CAPACITY; sm_index = index - 1; the
+   * session table and the KV as before the entry), and the CPU path takes
+   * the replica with its exported sessions.  With S = 0 nothing is
+   * allocated and a session entry makes the leader fall back before it
+   * appends (DRB_FB_ENTRY_TYPE), as it always has. */
+  uint32_t session_slots;
+  uint32_t session_history;
 } drb_config;
 
 /* One step round (engine.processSteps, engine.go:1304). */
@@ -906,7 +938,9 @@ typedef struct drb_worker_bufs {
 
 /* DRB_EAGAIN: b already has an export in flight (drb_worker_wait it
  * first), or 16 exports are in flight; two drb_worker_bufs alternate in a
- * step worker's loop */
+ * step worker's loop.  DRB_EINVAL on an engine with sessions
+ * (drb_config.session_slots > 0): a lane's one-word record cannot say
+ * rejected or cached; there the results go through drb_apply_results. */
 int drb_worker_export(drb_engine *e, uint32_t slot, const drb_worker_bufs *b);
 /* The same for one step worker's partition of the shards: the lanes whose
  * ShardID % n_parts == part (engine.go:1036-1049 processSteps over
@@ -1242,7 +1276,18 @@ int drb_exchange_mark(drb_engine *e);
  * is the count (DRB_ERANGE if more than cap).  Replicas handed to the CPU
  * path report nothing, except those whose apply stopped
  * (DRB_F_APPLY_STOPPED): their entries applied before the stop.
+ * With sessions (drb_config.session_slots) value and the bits of `ignored`
+ * are what the apply recorded for the entry: a register's or unregister's
+ * ClientID, an update's Result or the cached one of a repeated series; the
+ * host calls pendingProposals.applied(ClientID, SeriesID, Key, result,
+ * rejected) unless DRB_APPLY_IGNORED is set (node.go:243-257).
  */
+#define DRB_APPLY_IGNORED 1u  /* an empty no-op (statemachine.go:939-942), or
+                               * a session entry whose series was responded
+                               * to (:1071-1074): nothing to call */
+#define DRB_APPLY_REJECTED 2u /* ApplyUpdate(rejected = true): a duplicate
+                               * register, an unregister or an update of an
+                               * unknown client */
 typedef struct drb_apply_result {
   uint64_t group;      /* lane */
   uint64_t index;
@@ -1251,7 +1296,8 @@ typedef struct drb_apply_result {
   uint64_t series_id;
   uint64_t value;      /* sm.Result.Value */
   uint32_t slot;
-  uint32_t ignored;    /* 1: an empty no-op entry (statemachine.go:939-942) */
+  uint32_t ignored;    /* DRB_APPLY_IGNORED | DRB_APPLY_REJECTED bits; without
+                        * sessions 1 for an empty no-op entry, else 0 */
 } drb_apply_result;
 int drb_apply_results(drb_engine *e, uint32_t slot, uint64_t first_group,
                       uint64_t n_groups, drb_apply_result *out, size_t cap,
@@ -1290,6 +1336,39 @@ int drb_kv_import(drb_engine *e, uint64_t group, uint32_t slot,
 int drb_kv_export(drb_engine *e, uint64_t group, uint32_t slot, uint8_t *keys,
                   uint32_t *key_lens, uint8_t *vals, uint32_t *val_lens,
                   size_t cap, size_t *n_out);
+
+/* The client sessions of one replica (drb_config.session_slots > 0, else
+ * DRB_EINVAL), handed over with the replica on a fallback and put back, or
+ * loaded from a snapshot, before it runs again.  A session's responses are
+ * hist[first_history .. first_history + n_history). */
+typedef struct drb_session_rec {
+  uint64_t client_id;
+  uint64_t responded_up_to;  /* Session.RespondedUpTo */
+  uint32_t n_history;        /* len(Session.History) */
+  uint32_t first_history;
+} drb_session_rec;
+typedef struct drb_session_resp {
+  uint64_t series_id;
+  uint64_t value;            /* sm.Result.Value */
+} drb_session_resp;
+/* Sessions least recently used first -- lrusession.save's order
+ * (lrusession.go:93-120), so the host writes the snapshot's session image or
+ * rebuilds its LRU by adding them in turn -- each one's responses by
+ * ascending series.  *n / *n_hist: the counts; DRB_ERANGE, with the full
+ * counts, when they exceed cap / hist_cap. */
+int drb_sessions_export(drb_engine *e, uint64_t group, uint32_t slot,
+                        drb_session_rec *recs, size_t cap,
+                        drb_session_resp *hist, size_t hist_cap, size_t *n,
+                        size_t *n_hist);
+/* Replaces the replica's table with n sessions in that order.  DRB_ERANGE,
+ * the table unchanged: more than session_slots sessions, more than
+ * session_history responses in one, a value >= 2^62, a zero or repeated
+ * client_id, a repeated series_id in a session or one at or below its
+ * responded_up_to.  drb_import_replicas and drb_kv_import do not touch the
+ * sessions. */
+int drb_sessions_import(drb_engine *e, uint64_t group, uint32_t slot,
+                        const drb_session_rec *recs, size_t n,
+                        const drb_session_resp *hist, size_t n_hist);
 
 /* --- codecs (raftpb EntryBatch encode / CRC path) ---------------------- */
 
@@ -1463,7 +1542,9 @@ int drb_tan_scan(const uint8_t *log, size_t len, drb_tan_scan_rec *out,
  * base_index / base_term name the entry the logs continue from (a snapshot
  * index; R + 1 at its term for logs of an engine started by
  * drb_init_steady).  Entries at or below it are skipped.  The KV is not
- * cleared: what drb_kv_import put there is the snapshot.
+ * cleared: what drb_kv_import put there is the snapshot.  The same holds
+ * for the session table (drb_config.session_slots): the replay's session
+ * entries apply onto what drb_sessions_import put there.
  *
  * Pass 1 validates every replica (checksums, structure, every Update and
  * entry header) and writes nothing; pass 2 places the kept records' entries
@@ -1480,18 +1561,19 @@ int drb_tan_scan(const uint8_t *log, size_t len, drb_tan_scan_rec *out,
  *   DRB_REC_MISMATCH     a record of another ShardID / ReplicaID
  *   DRB_REC_GAP          entries not contiguous from base_index + 1
  *   DRB_REC_ENTRY_TYPE   an entry above the base the device apply refuses
- *                        (config change, session-managed series, Snappy
- *                        without entry_compression)
+ *                        (config change; session-managed series without
+ *                        session_slots, Snappy without entry_compression)
  *   DRB_REC_CAPACITY     a Cmd above cmd_cap, or entries still to be
  *                        applied that have left the window: the log reached
  *                        W or more indexes beyond them before their commit
  *                        was persisted, a tail that an overwrite cut off
  *                        again included
  *   DRB_REC_SNAPSHOT     a record that carries a Snapshot
- *   DRB_REC_APPLY_STOPPED  the KV or its value pool filled, or a payload
- *                        the KV does not take, while applying: the one
- *                        status reached after the KV was touched -- the host
- *                        imports that replica's KV again
+ *   DRB_REC_APPLY_STOPPED  the KV, its value pool or the session table
+ *                        filled, or a payload the KV does not take, while
+ *                        applying: the one status reached after the KV (and
+ *                        the sessions) were touched -- the host imports
+ *                        that replica's KV and sessions again
  * A replica with any status from DRB_REC_CORRUPT on is marked
  * DRB_F_FALLBACK with DRB_FB_RECOVERY and otherwise unchanged (its restart
  * goes the CPU way: drb_import_replicas, drb_import_log, drb_kv_import).
