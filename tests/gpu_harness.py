@@ -396,15 +396,22 @@ class DistPair:
         Engine.exchange_local(self.engs, counted=self.counted)
 
     def round(self, k=1, tick=False, read_index=False, groups=None,
-              exchange=True):
+              exchange=True, batch=None):
+        """batch=(counts, k, ents, eents, pool): a caller-built batch in
+        place of the seeded one -- ents [g][k] for the oracle, eents
+        [g][max_props] (global groups) for the engines."""
         salt = self.rounds
         if self.cpu:  # no client input for groups on the CPU path
             groups = [g for g in (range(self.G) if groups is None else groups)
                       if g not in self.cpu]
         pin = ri_in = abi.DRB_NONE
+        eents = None
+        if batch is not None:
+            counts, k, ents, eents, pool = batch
         if k:
-            counts, ents, pool = workload.build_batch(
-                self.G, k, self.seed, salt, 256, 4, groups)
+            if batch is None:
+                counts, ents, pool = workload.build_batch(
+                    self.G, k, self.seed, salt, 256, 4, groups)
             self.orc.stage_proposals(counts, k, ents, pool)
             for r, e in enumerate(self.engs):
                 mp = e.cfg["max_props"]
@@ -416,7 +423,8 @@ class DistPair:
                         continue
                     ec[j] = counts[g]
                     for q in range(counts[g]):
-                        ee[j * mp + q] = ents[g * k + q]
+                        ee[j * mp + q] = ents[g * k + q] if eents is None \
+                            else eents[g * mp + q]
                 e.stage_proposals(0, ec, ee, pool)
             pin = 0
         if read_index:

@@ -119,8 +119,12 @@ class Model:
         self.applied = 0
 
     # outcome classes, named as the device names them (drb_session.hpp)
-    def apply(self, client_id, series_id, responded_to, typ, cmd):
-        """handleEntry: ((value, rejected, ignored), outcome class)."""
+    def apply(self, client_id, series_id, responded_to, typ, cmd,
+              payload=get_payload):
+        """handleEntry: ((value, rejected, ignored), outcome class).
+        payload(typ, cmd) is GetPayload: this module's for uncompressed
+        entries, the oracle's (po.get_payload) where Cmds are Snappy blocks;
+        Result.Value is the decoded payload's length (kvtest.go:161)."""
         self.applied += 1
         assert typ != ENTRY_CONFIG_CHANGE
         if client_id == 0:  # not session managed
@@ -147,10 +151,11 @@ class Model:
             v = s.get_response(series_id)
             if v is not None:
                 return (v, False, False), "cached"
-        key, val = pbkv(get_payload(typ, cmd))
+        data = payload(typ, cmd)
+        key, val = pbkv(data)
         self.kv[key] = val
         self.count += 1
-        value = len(get_payload(typ, cmd))
+        value = len(data)
         if s is not None:
             s.add_response(series_id, value)
         return (value, False, False), "update" if s else "noop-session"

@@ -10,8 +10,6 @@ the batch for everything raft, and tests/session_model.py -- the reference's
 session code in plain Python, pinned by the reference's own tests in
 tests/test_session_model.py -- for the state machine.
 """
-import struct
-
 import pytest
 
 from dragonboat_amd import abi, workload
@@ -20,7 +18,8 @@ from oracle import pyoracle as po
 from tests import session_model as sm
 from tests import tan_images as ti
 from tests import tan_mux_images as tm
-from tests.session_harness import REG, UNREG, SessPair, ent, pbkv
+from tests.session_harness import (REG, UNREG, SessPair, cl, ent, pbkv,
+                                   script_rounds, val)
 from tests.test_gpu_elections import _unhost
 
 pytestmark = pytest.mark.gpu
@@ -28,15 +27,6 @@ pytestmark = pytest.mark.gpu
 G = 96  # a full wave and a partial one
 SEED = 0x5EEDD8B0
 ALL = {(w, s) for w in (0, 1) for s in range(3)}
-
-
-def cl(g, n):
-    """Client n of group g: ids over the whole 64 bits, never 0."""
-    return workload.mix64(0xC11E + 8 * g + n) | 1
-
-
-def val(g):
-    return struct.pack("<I", workload.mix64(g) & 0xffffffff)
 
 
 def lifecycle(g):
@@ -62,17 +52,8 @@ def lifecycle(g):
 def run_script(p, steps, per_round=3, drain=4, **kw):
     """Group g's steps, per_round a round, its phase g % 4 rounds late;
     ticks and ReadIndex rounds mixed in; every round checked."""
-    n = max(len(steps(g)) for g in range(p.G))
-    rounds = (n + per_round - 1) // per_round + 3
-    for r in range(rounds + drain):
-        rows = {}
-        for g in range(p.G):
-            q = r - g % 4
-            part = steps(g)[per_round * q:per_round * (q + 1)] if q >= 0 \
-                else []
-            if part:
-                rows[g] = part
-        p.sess_round(rows, tick=(r % 2 == 0), read_index=(r % 3 == 0), **kw)
+    for rows, tick, ri in script_rounds(p.G, steps, per_round, drain):
+        p.sess_round(rows, tick=tick, read_index=ri, **kw)
     for g in range(p.G):
         sts = p.eng.export_replicas(g, 1)
         assert all(a.sm_index == a.last_index == sts[0].last_index

@@ -149,10 +149,19 @@ class TwoNodes:
         self.rounds = 0
         self.wire_bytes = 0
 
-    def round(self, k=1, tick=False, read_index=False, val_len=4):
+    def round(self, k=1, tick=False, read_index=False, val_len=4,
+              batch=None):
+        """batch=(counts, k, ents, eents, pool): a caller-built batch in
+        place of the seeded one -- ents [g][k] for the oracle, eents
+        [g][max_props] for the leaders' engine."""
         from dragonboat_amd import abi, workload
         pin = ri_in = abi.DRB_NONE
-        if k:
+        if batch is not None:
+            counts, k, ents, eents, pool = batch
+            self.orc.stage_proposals(counts, k, ents, pool)
+            self.lead.stage_proposals(0, counts, eents, pool)
+            pin = 0
+        elif k:
             counts, ents, pool = workload.build_batch(
                 self.G, k, self.seed, self.rounds, 256, val_len, None)
             self.orc.stage_proposals(counts, k, ents, pool)

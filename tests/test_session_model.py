@@ -145,3 +145,26 @@ def test_clear_to_equals_drop_every_key_at_or_below():
                 upto = max(upto, to)
                 assert s.responded_up_to == upto
                 assert s.history == (keep if drop_all else before)
+
+
+def test_snappy_update_value_is_the_decoded_length_and_is_cached():
+    """Model.apply with the oracle's GetPayload: a Snappy-encoded update's
+    Result.Value is the decoded payload's length (kvtest.go:161), not the
+    Cmd's, and a retry of the series is served that value from the history
+    without a second Update."""
+    from oracle import pyoracle as po
+    from tests import snappy_blocks as sb
+    data = po.pbkv_marshal(b"test-key", b"z" * 200)
+    cmd = sb.checked(sb.compress(data), data)
+    assert len(cmd) < len(data) // 2
+    m = sm.Model()
+    register(m)
+    first = m.apply(CID, 1, 0, sm.ENTRY_ENCODED, cmd, po.get_payload)
+    assert first == ((len(data), False, False), "update")
+    assert m.kv[b"test-key"] == b"z" * 200 and m.count == 1
+    again = m.apply(CID, 1, 0, sm.ENTRY_ENCODED, cmd, po.get_payload)
+    assert again == ((len(data), False, False), "cached")
+    assert m.count == 1 and m.sessions() == [(CID, 0, {1: len(data)})]
+    # the default payload function still refuses a compressed Cmd
+    with pytest.raises(AssertionError):
+        sm.Model().apply(0x77, 0, 0, sm.ENTRY_ENCODED, cmd)
