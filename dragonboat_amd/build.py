@@ -3,9 +3,11 @@
 hipcc cross-compiles for gfx950 without a GPU; the .so is built in-tree so
 it travels to the GPU box with the repository snapshot.
 
-The step kernel has 80 instantiations (R = 1..8 replicas per group x nine
-kinds, drb_launch.hpp, the lean kernel's two among them, and the four LOCAL
-kinds for R = 3 and 5).  Each is its own translation unit
+The step kernel has 80 instantiations: the kinds of csrc/drb_kinds.hpp, each
+for the values of R (replicas per group) its row names -- nine kinds, the
+lean kernel's two among them, for R = 1..8 and the four LOCAL kinds for
+R = 3 and 5.  That table is parsed here; this file keeps no kind numbers of
+its own.  Each instantiation is its own translation unit
 (drb_step_inst.hip compiled with -DDRB_INST_R / -DDRB_INST_KIND), so the
 objects build in parallel and only the ones whose sources changed rebuild;
 the engine's host code and auxiliary kernels are drb_engine.hip, the tan
@@ -15,6 +17,7 @@ drb_recover_mux.hpp with its hipCUB scan and sort) units of their own.
 """
 import hashlib
 import os
+import re
 import subprocess
 import sys
 import time
@@ -28,22 +31,20 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC",
          "-Wno-pass-failed"]
-NUM_KINDS = 9
-# the LOCAL kinds 9-12 (drb_launch.hpp), for these R only
-LOCAL_KINDS, LOCAL_R = (9, 10, 11, 12), (3, 5)
-# the headers a step-kernel instantiation includes
-STEP_DEPS = ["drb_step_inst.hip", "drb_step.hpp", "drb_lean.hpp",
-             "drb_launch.hpp",
+# what a step-kernel instantiation includes: its launcher's two headers,
+# then the kernel's
+STEP_DEPS = ["drb_step_inst.hip", "drb_launch.hpp", "drb_kinds.hpp",
+             "drb_step.hpp", "drb_lean.hpp",
              "drb_layout.hpp", "drb_msg.hpp", "drb_codec.hpp", "drb_ring.hpp",
              "drb_snappy.hpp", "drb_session.hpp"]
 # the recovery kernels' (drb_recover_inst.hip): the step kernel's headers
 # (apply_entry), the tan read path and the multiplexed logs' index
-RECOVER_DEPS = STEP_DEPS[1:] + ["drb_recover_inst.hip", "drb_recover.hpp",
+RECOVER_DEPS = STEP_DEPS[3:] + ["drb_recover_inst.hip", "drb_recover.hpp",
                                 "drb_tanread.hpp", "drb_recover_mux.hpp",
                                 "drb_tanmux.hpp"]
 # the tan record kernels' (drb_tan_inst.hip)
 TAN_DEPS = ["drb_tan_inst.hip", "drb_tan.hpp", "drb_launch.hpp",
-            "drb_layout.hpp", "drb_codec.hpp", "drb_ring.hpp"]
+            "drb_kinds.hpp", "drb_layout.hpp", "drb_codec.hpp", "drb_ring.hpp"]
 
 
 def _inc():
@@ -54,6 +55,20 @@ def _deps():
     """Every source and header the engine includes (all of csrc/)."""
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))
             if f.endswith((".hip", ".hpp"))] + [_inc()]
+
+
+def step_kinds():
+    """[(kind number, the R it is built for)] of csrc/drb_kinds.hpp: the
+    rows of DRB_STEP_KINDS, each with its DRB_FOR_<set> list of R."""
+    with open(os.path.join(CSRC, "drb_kinds.hpp")) as f:
+        text = f.read().replace("\\\n", " ")
+    sets = {m.group(1): [int(r) for r in re.findall(r"X\((\d+), K\)",
+                                                    m.group(2))]
+            for m in re.finditer(r"#define DRB_FOR_(\w+)\(X, K\)(.*)", text)}
+    table = re.search(r"#define DRB_STEP_KINDS\(X\)(.*)", text).group(1)
+    rows = [[c.strip() for c in r.split(",")]
+            for r in re.findall(r"X\(([^)]*)\)", table)]
+    return [(int(row[1]), sets[row[8]]) for row in rows]
 
 
 def _units(defines):
@@ -67,12 +82,13 @@ def _units(defines):
               tan_deps),
              ("tan_select.o", "drb_tan_inst.hip", ["DRB_TAN_KERNELS=1"],
               tan_deps)]
+    kinds = step_kinds()
     for r in range(1, 9):
-        for k in list(range(NUM_KINDS)) + \
-                (list(LOCAL_KINDS) if r in LOCAL_R else []):
-            units.append(("step_r%d_k%d.o" % (r, k), "drb_step_inst.hip",
-                          ["DRB_INST_R=%d" % r, "DRB_INST_KIND=%d" % k],
-                          step_deps))
+        for k, built_for in kinds:
+            if r in built_for:
+                units.append(("step_r%d_k%d.o" % (r, k), "drb_step_inst.hip",
+                              ["DRB_INST_R=%d" % r, "DRB_INST_KIND=%d" % k],
+                              step_deps))
     return units
 
 

@@ -1046,6 +1046,12 @@ extern "C" int drb_init_steady(drb_engine *e, uint64_t term,
   dim3 grid((unsigned)((e->v.G + 255) / 256), e->v.R);
   k_init_steady<<<grid, 256, 0, e->stream>>>(e->v, term, leader_slot, seed);
   HIPCHK(hipGetLastError());
+  // a group of one elected itself without a message, so its setup recorded
+  // no activity (quiesce.go:56-74): idleSince stays 0, not the election
+  // round's tick that k_init_steady writes
+  if (e->v.quiesce && e->v.R == 1)
+    HIPCHK(hipMemsetAsync(e->v.u64 + u64_ix(e->v, F_QS_IDLE, 0, 0), 0,
+                          e->v.G * sizeof(uint64_t), e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return refresh_roles(e);
 }
@@ -2059,22 +2065,40 @@ __global__ __launch_bounds__(256) void k_active_scatter(const View v) {
   }
 }
 
-// the largest round (workgroups of both launches) whose leader and
-// follower launches run side by side (C2, 768 workgroups: 0.0882 against
-// 0.0928 ms/round on one stream, profiles/r05_chunk)
-constexpr uint64_t kSplitMaxBlocks = 2048;
+// kStepLaunch.fn[R - 1][kind]: the kind's launcher (drb_step_inst.hip), its
+// stand-in's where the kind is not built for R (drb_kinds.hpp)
+struct StepLaunchTable {
+  StepLaunchFn fn[8][NUM_STEP_KINDS] = {};
+  constexpr StepLaunchTable() {
+#define DRB_SET_STEP_LAUNCH(R, K) fn[R - 1][K] = DRB_STEP_LAUNCH_NAME(R, K);
+#define DRB_X(name, num, kernel, L, E, S, F, LOC, set, alt) \
+  DRB_FOR_##set(DRB_SET_STEP_LAUNCH, num)
+    DRB_STEP_KINDS(DRB_X)
+#undef DRB_X
+#undef DRB_SET_STEP_LAUNCH
+    for (int R = 1; R <= 8; ++R)
+      for (int k = 0; k < NUM_STEP_KINDS; ++k)
+        fn[R - 1][k] = fn[R - 1][step_kind_at(R, k)];
+  }
+};
+static constexpr StepLaunchTable kStepLaunch;
 
-// blk0 / nblk: a chunk of group blocks (drb_step_rounds; nblk 0: all), on
-// stream st
-template <int R>
-static void launch_step(drb_engine *e, const RoundParams &p0,
-                        hipStream_t st = nullptr, uint32_t blk0 = 0,
-                        uint32_t nblk = 0) {
+// One round's launches, as plan_step (drb_kinds.hpp) chose them.  blk0 /
+// nblk: a chunk of group blocks (drb_step_rounds; nblk 0: all), on stream st
+static int launch_step(drb_engine *e, const RoundParams &p0,
+                       hipStream_t st = nullptr, uint32_t blk0 = 0,
+                       uint32_t nblk = 0) {
   const unsigned gx_all = (unsigned)((e->v.G + 255) / 256);
   const unsigned gx = nblk ? nblk : gx_all;
   if (!st) st = e->stream;
+  if (e->v.R < 1 || e->v.R > 8) return DRB_EINVAL;
   if (p0.listed) {
-    k_active_scan<R><<<gx, 256, 0, e->stream>>>(e->v, p0);
+    switch (e->v.R) {
+#define DRB_X(R, K) \
+  case R: k_active_scan<R><<<gx, 256, 0, e->stream>>>(e->v, p0); break;
+      DRB_FOR_ALL_R(DRB_X, )
+#undef DRB_X
+    }
     k_active_prefix<<<4 * e->v.R, 1024, 0, e->stream>>>(e->v, gx);
     k_active_scatter<<<dim3(gx, e->v.R), 256, 0, e->stream>>>(e->v);
   }
@@ -2084,76 +2108,52 @@ static void launch_step(drb_engine *e, const RoundParams &p0,
   uint32_t nl = 0, nf = 0;
   pl.slots = slot_list(e->role_slots[0], &nl);
   pf.slots = slot_list(e->role_slots[1], &nf);
-  // the EXT instantiation only where its paths can run (drb_step.hpp)
-  const bool ext =
-      e->v.C16 > 4 || e->v.kv_ool || p0.encode_saves || e->v.quiesce ||
-      e->v.kv_ovf_cap || e->v.snappy || e->v.sessions;
   pl.nrows = nl;
   pf.nrows = nf;
+  const StepPlan plan =
+      plan_step(e->v, p0.encode_saves, p0.listed, nl, nf, gx,
+                !nblk && st == e->stream, e->no_lean);
   // one-dimensional grids of the role's slot rows, row-major (block_pos);
   // both launches back to back on the engine stream (they touch disjoint
   // state; on two streams they measured 3 % slower at C3)
-  const StepLaunchFn *launch = kStepLaunch[R - 1];
-  // forwarded proposals and member kinds: the EXT kernels with the Propose
-  // and nonVoting / witness paths
-  const bool fwd = e->v.fwd_props || e->v.nv_mask || e->v.wt_mask;
-  // without placement (no remote planes) the LOCAL instantiations, which
-  // compile the remote-plane paths out (drb_launch.hpp)
-  const bool local = !e->v.remote_mask;
-  const int kl = fwd ? SK_LEAD_FWD
-                 : ext ? (local ? SK_LEAD_EXT_LOCAL : SK_LEAD_EXT)
-                       : (local ? SK_LEAD_LOCAL : SK_LEAD);
-  const int kf = fwd ? SK_FOLLOW_FWD
-                 : ext ? (local ? SK_FOLLOW_EXT_LOCAL : SK_FOLLOW_EXT)
-                       : (local ? SK_FOLLOW_LOCAL : SK_FOLLOW);
-  // a small round (C2: 64k groups, 768 workgroups, one wave per SIMD) runs
-  // its two launches side by side on the engine's two streams: they touch
-  // disjoint state, and neither fills the chip alone
-  const bool split = nl && nf && !nblk && !e->v.elections &&
-                     st == e->stream &&
-                     (uint64_t)gx * (nl + nf) <= kSplitMaxBlocks;
-  if (split) {
+  const StepLaunchFn *launch = kStepLaunch.fn[e->v.R - 1];
+  if (plan.split) {
     (void)hipEventRecord(e->ev_fork, st);
     (void)hipStreamWaitEvent(e->stream2, e->ev_fork, 0);
   }
-  // listed rounds of a plain EXT engine: the light lanes' heartbeat rounds
-  // through the lean kernel first (drb_lean.hpp), the full kernel then
-  // over the heavy lanes and the ones the lean kernel escalated
-  const bool lean = p0.listed && ext && !fwd && !nblk &&
-                    !e->v.elections && !e->v.remote_mask &&
-                    !e->v.save_tan && !e->v.save_batched && !e->no_lean &&
-                    st == e->stream;
-  if (lean) {
+  if (plan.lean) {
     // the lean kernels, then the full ones over the heavy and the
     // escalated lanes, one stream.  Measured slower on two streams: the
     // heavy lanes' full launches beside the lean kernels (2.02 against 1.97
     // ms a C5 round), the two full launches side by side (1.92 against
     // 1.90), the two lean ones (1.93), both pairs (1.96;
     // profiles/r06_lean/c5_streams_ab.txt).
-    if (split) {
+    if (plan.split) {
       (void)hipEventRecord(e->ev_join, e->stream2);
       (void)hipStreamWaitEvent(st, e->ev_join, 0);
     }
     if (nl) launch[SK_LEAD_LEAN](e->v, pl, gx * nl, st);
     if (nf) launch[SK_FOLLOW_LEAN](e->v, pf, gx * nf, st);
     pl.lean = pf.lean = LEAN_ALL;
-    if (nl) launch[kl](e->v, pl, gx * nl, st);
-    if (nf) launch[kf](e->v, pf, gx * nf, st);
-    return;
+    if (nl) launch[plan.lead](e->v, pl, gx * nl, st);
+    if (nf) launch[plan.follow](e->v, pf, gx * nf, st);
+  } else {
+    if (nl) launch[plan.lead](e->v, pl, gx * nl, st);
+    if (nf)
+      launch[plan.follow](e->v, pf, gx * nf, plan.split ? e->stream2 : st);
+    if (plan.split) {
+      (void)hipEventRecord(e->ev_join, e->stream2);
+      (void)hipStreamWaitEvent(st, e->ev_join, 0);
+    }
+    if (plan.slow) {
+      RoundParams ps = p0;
+      ps.slots = 0;
+      ps.nrows = 1;
+      launch[SK_SLOW](e->v, ps, (e->v.slow_cap + 255) / 256, e->stream);
+    }
   }
-  hipStream_t sf = split ? e->stream2 : st;
-  if (nl) launch[kl](e->v, pl, gx * nl, st);
-  if (nf) launch[kf](e->v, pf, gx * nf, sf);
-  if (split) {
-    (void)hipEventRecord(e->ev_join, e->stream2);
-    (void)hipStreamWaitEvent(st, e->ev_join, 0);
-  }
-  if (e->v.elections) {  // the replicas the two launches routed (F_SLOW)
-    RoundParams ps = p0;
-    ps.slots = 0;
-    ps.nrows = 1;
-    launch[SK_SLOW](e->v, ps, (e->v.slow_cap + 255) / 256, e->stream);
-  }
+  HIPCHK(hipGetLastError());
+  return DRB_OK;
 }
 
 // role map: bit s of role_slots[0] when a hosted replica of slot s is a
@@ -2268,24 +2268,6 @@ static int round_params(drb_engine *e, const drb_round_in *in, uint64_t ahead,
   return DRB_OK;
 }
 
-static int launch_any(drb_engine *e, const RoundParams &p,
-                      hipStream_t st = nullptr, uint32_t blk0 = 0,
-                      uint32_t nblk = 0) {
-  switch (e->v.R) {
-    case 1: launch_step<1>(e, p, st, blk0, nblk); break;
-    case 2: launch_step<2>(e, p, st, blk0, nblk); break;
-    case 3: launch_step<3>(e, p, st, blk0, nblk); break;
-    case 4: launch_step<4>(e, p, st, blk0, nblk); break;
-    case 5: launch_step<5>(e, p, st, blk0, nblk); break;
-    case 6: launch_step<6>(e, p, st, blk0, nblk); break;
-    case 7: launch_step<7>(e, p, st, blk0, nblk); break;
-    case 8: launch_step<8>(e, p, st, blk0, nblk); break;
-    default: return DRB_EINVAL;
-  }
-  HIPCHK(hipGetLastError());
-  return DRB_OK;
-}
-
 // the host's bookkeeping after round p was enqueued
 static void round_done(drb_engine *e, const RoundParams &p) {
   e->round++;
@@ -2320,7 +2302,7 @@ extern "C" int drb_step_round_async(drb_engine *e, const drb_round_in *in) {
     HIPCHK(hipMemsetAsync(e->v.xslow, 0,
                           4ull * e->v.R * e->v.R * ((e->v.G + 255) / 256) * 4,
                           e->stream));
-  if (int rc = launch_any(e, p)) return rc;
+  if (int rc = launch_step(e, p)) return rc;
   if (p.encode_saves && e->v.save_tan) {
     int rc = launch_tan(e, (uint32_t)p.round);
     if (rc) return rc;
@@ -2366,13 +2348,13 @@ extern "C" int drb_step_rounds(drb_engine *e, const drb_round_in *in,
     // two role launches side by side where they fit (launch_step), the
     // host's per-round cost one C call's (C2: a Python call per round left
     // the GPU idle a third of the time, profiles/r06_c2)
-    for (uint32_t t = 0; t < k && !rc; ++t) rc = launch_any(e, ps[t]);
+    for (uint32_t t = 0; t < k && !rc; ++t) rc = launch_step(e, ps[t]);
   } else {
     for (uint64_t c0 = 0, c = 0; c0 < gx && !rc; c0 += cb, ++c) {
       const uint32_t nb = (uint32_t)std::min<uint64_t>(cb, gx - c0);
       hipStream_t st = (c & 1) ? e->stream2 : e->stream;
       for (uint32_t t = 0; t < k && !rc; ++t)
-        rc = launch_any(e, ps[t], st, (uint32_t)c0, nb);
+        rc = launch_step(e, ps[t], st, (uint32_t)c0, nb);
     }
   }
   // the second stream joins the engine stream whatever happened

@@ -1,7 +1,7 @@
 #!/bin/bash
 # VGPR / SGPR / spill / LDS / occupancy of the step kernels.
 # usage: tools/regs.sh [R] [kinds...] [-- extra hipcc flags]
-#   kinds: 0 lead, 1 lead ext, 2 follow, 3 follow ext, 4 raft launch
+#   kinds: the numbers of dragonboat_amd/csrc/drb_kinds.hpp's table
 R=${1:-3}; shift
 kinds=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do kinds+=("$1"); shift; done
